@@ -11,24 +11,30 @@ per second, summed over ranks.
 Multi-GPU (BASELINE.json configs[4]): chunks are independent, so
 rank r owns a contiguous slice of ONE seeded chunk list and no collective sits
 on the data path (no RCCL: the start/stop barrier and the two scalar
-reductions run over gloo).  Two modes, both in the JSON line when N > 1 or
---config5 is given:
+reductions run over gloo).  Two modes, both in the JSON line with --full at
+N > 1 or with --config5:
   weak   (the headline `value`): --chunks per GPU, the list has N x chunks;
   strong (`config5_strong`):     --total-chunks (default 163 840 = 10 GiB) in
                                  all, rank r gets [r*ceil(B/N), (r+1)*ceil(B/N)).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 `--gpus N` with N > 1 needs no launcher: when WORLD_SIZE is not set the process
 starts N child ranks itself, before anything touches the GPU.  Under
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it
 is one of the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
-`roofline` (dominant kernel = the LZ4 compress kernel, HBM-bound model),
-`cpu_baseline` (system liblz4 on the host cores, bounded sample) and, at N = 1,
+Prints ONE JSON line on rank 0 with the headline (`value`, `ms_per_step`: the
+wall time of one of the K timed steps) and its `roofline` (dominant kernel =
+the LZ4 compress kernel, HBM-bound model).  A plain run measures the headline
+and nothing else.  `--full` adds `cpu_baseline` (system liblz4 on the host
+cores, bounded sample), the strong-scaling row at N > 1 and, at N = 1,
 `extra_keys`: every other BASELINE config (LZ4 distributions x data types at
 the full 100 000 chunks, Snappy on TPC-H-like text, Cascaded on sorted
 columns), each with its own HBM fraction, ratio and CPU baseline.
+
+`--dump-outputs DIR` writes what the headline's last timed step handed its
+caller as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -232,6 +238,42 @@ class CodecJob:
 
     def compressed_bytes(self) -> int:
         return int(self.comp.sizes.sum().item())
+
+
+DUMP_SAMPLE_CHUNKS = 64
+DUMP_SAMPLE_SEED = 0x5EED00D0
+
+
+def dump_outputs(job: CodecJob, out_dir: str):
+    """Writes what the job's last compress + decompress handed its caller, as float32 .npy files (every value is
+    an exact integer below 2^24): per chunk the compressed size, the decompressed size and the status, and for a
+    fixed, seeded sample of DUMP_SAMPLE_CHUNKS chunks the compressed stream and the decompressed chunk, one row
+    each, zero past the chunk's size.  About 35 MB at 100 000 chunks: 12 bytes per chunk + 2 x 64 x 64 KiB x 4,
+    within 64 MB up to 2 million chunks (more than one GPU holds with its three buffers)."""
+    import numpy as np
+    import torch
+    if job.comp.data.is_cuda:
+        torch.cuda.synchronize()
+    n = job.n
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(DUMP_SAMPLE_CHUNKS, n), replace=False))
+    idx = torch.from_numpy(pick).to(job.comp.sizes.device)
+
+    def sample(batch, sizes):
+        rows = batch.data[:n * batch.stride].view(n, batch.stride)[idx]
+        keep = torch.arange(batch.stride, device=rows.device)[None, :] < sizes[idx][:, None]
+        return torch.where(keep, rows, torch.zeros_like(rows)).to(torch.float32)
+
+    out = {
+        "sample_chunks": torch.from_numpy(pick.astype(np.float32)),
+        "compressed_sizes": job.comp.sizes.to(torch.float32),
+        "compressed_sample": sample(job.comp, job.comp.sizes),
+        "decompressed_sizes": job.actual.to(torch.float32),
+        "decompressed_sample": sample(job.out, job.actual),
+        "statuses": job.statuses.to(torch.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def time_phases(job: CodecJob, steps: int):
@@ -477,8 +519,11 @@ def kernel_source_id(read=None) -> str:
 def device_asm_id():
     """Identifies the DEVICE code of the build at hand: sha256 over the assembly the kernel objects were made from
     (csrc/build/*.gfx950.s, kept by the Makefile).  A change to host code or comments in a kernel source file
-    changes kernel_source_id() but not this; None when the build directory is not there."""
+    changes kernel_source_id() but not this; None when the build directory is not there.  hipcc names each
+    compilation unit __hip_cuid_<hash of its command line>, which holds the path of the checkout: that name is
+    left out, so the same device code has the same id wherever it was built."""
     import glob
+    import re
     files = sorted(glob.glob(os.path.join(ROOT, "hipcomp-core_amd", "csrc", "build", "*.gfx950.s")))
     if not files:
         return None
@@ -486,7 +531,7 @@ def device_asm_id():
     for path in files:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
-            h.update(f.read())
+            h.update(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", f.read()))
     return h.hexdigest()[:16]
 
 
@@ -539,7 +584,7 @@ def main():
     ap.add_argument("--total-chunks", type=int, default=CONFIG5_TOTAL,
                     help="chunks in all for the strong-scaling row (BASELINE config 5: 10 GiB)")
     ap.add_argument("--config5", dest="config5", action="store_true", default=None,
-                    help="also run the strong-scaling row at N = 1 (default: only when N > 1)")
+                    help="also run the strong-scaling row (default: only with --full at N > 1)")
     ap.add_argument("--no-config5", dest="config5", action="store_false")
     ap.add_argument("--dist", default="uniform", choices=["uniform", "harness", "runs"])
     ap.add_argument("--dtype", default="char", choices=["char", "int"])
@@ -552,6 +597,12 @@ def main():
                     help="skip the extra rows (other distributions / data types / codecs)")
     ap.add_argument("--variant-chunks", type=int, default=100000)
     ap.add_argument("--text-chunks", type=int, default=65536, help="chunks of TPC-H-like text for the config-4 rows (4 GiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure what a plain run leaves out: the CPU baselines, at N = 1 every "
+                         "other BASELINE config (extra_keys), at N > 1 the strong-scaling row")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the chunks' bytes): see dump_outputs")
     ap.add_argument("--dry-run", action="store_true",
                     help="process plumbing only (spawn, rendezvous, barrier, slice arithmetic, reductions) with no "
                          "GPU and no codec call; prints a line whose value is null -- for the CPU tests")
@@ -644,6 +695,8 @@ def main():
     # ---- headline: weak scaling, rank r owns chunks [r*chunks, (r+1)*chunks) of one list
     lo, hi = shard_slice(args.chunks * world, world, rank)
     data, job, tc, td, value, wall = run_job(lo, hi, 0x5EED0002)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
     n_bytes, c_bytes = job.total, job.compressed_bytes()
     ms_step = wall / args.steps * 1e3
     res = None
@@ -685,14 +738,14 @@ def main():
                     "compressed_sizes_identical": same,
                 }
                 del rjob
-        if not args.no_cpu and world == 1:  # reported at N=1 only
+        if args.full and not args.no_cpu and world == 1:  # reported at N=1 only
             k = min(args.cpu_sample_chunks, job.n)
             res["cpu_baseline"] = cpu_liblz4_baseline(data[: k * CHUNK].cpu().numpy())
     del job, data
     torch.cuda.empty_cache()
 
     # ---- BASELINE config 5: ONE list of --total-chunks, strong scaling
-    want5 = args.config5 if args.config5 is not None else world > 1
+    want5 = args.config5 if args.config5 is not None else (args.full and world > 1)
     if want5:
         lo, hi = shard_slice(args.total_chunks, world, rank)
         data, job, tc5, td5, value5, wall5 = run_job(lo, hi, 0x5EED0002)
@@ -706,7 +759,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- every other BASELINE config, N = 1 only
-    if rank == 0 and args.variants and world == 1:
+    if rank == 0 and args.full and args.variants and world == 1:
         rows = []
         vc = args.variant_chunks
         seeds = {"uniform": 0x5EED0002, "harness": 0x5EED0003, "runs": 0x5EED0004}
