@@ -31,11 +31,10 @@
 // SURVEY.md App. C.4) are written as 0 here, so the output is deterministic.
 
 #include "cascaded_launch.hpp"
-#include "lz4_launch.hpp" // num_cus_of_current_device
+#include "device_facts.hpp"
 #include "placement.hiph"
 #include "wave_utils.hpp"
 
-#include <atomic>
 #include <type_traits>
 
 #define HC_LDS __attribute__((address_space(3)))
@@ -2386,22 +2385,13 @@ hipError_t launch_decompress(
   // registers, whichever is short first: every wave takes the same number of partitions, so a
   // workgroup that has to wait for a slot makes the launch twice as long (met in round 4: 21 by LDS,
   // 20 by registers, 5376 workgroups launched, 12.8 waves per CU at work on average).
-  static std::atomic<int> g_per_cu[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int cached = dev >= 0 && dev < 16 ? g_per_cu[dev].load(std::memory_order_acquire) : 0;
-  if (cached == 0) {
-    int by_api = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_api, reinterpret_cast<const void*>(k), kWave, lds) != hipSuccess || by_api < 1)
-      by_api = 1;
-    const int by_lds = (int)((160u * 1024u) / ((lds + 1279u) / 1280u * 1280u));
-    cached = by_api < by_lds ? by_api : by_lds;
-    if (cached > 32)
-      cached = 32;
-    if (dev >= 0 && dev < 16)
-      g_per_cu[dev].store(cached, std::memory_order_release);
-  }
-  const uint32_t per_cu = (uint32_t)cached;
+  uint32_t per_cu = (uint32_t)resident_per_cu(reinterpret_cast<const void*>(k), kWave, lds);
+  if (per_cu < 1)
+    per_cu = 1;
+  if (per_cu > groups_by_lds(lds))
+    per_cu = groups_by_lds(lds);
+  if (per_cu > 32)
+    per_cu = 32;
   const size_t resident = (size_t)num_cus_of_current_device() * per_cu;
   k<<<dim3((unsigned)(batch < resident ? batch : resident)), dim3(kWave), lds, stream>>>(
       comp_ptrs, comp_bytes, out_caps, batch, out_ptrs, actual_bytes, statuses);
@@ -2431,32 +2421,22 @@ void cascaded_launch_compress(
 
 namespace {
 typedef void (*PlacedKernel)(const uint8_t* const*, const size_t*, size_t*, uint32_t, int, int, int, int, uint32_t*, Placement);
-struct PlacedShape { PlacedKernel k; uint32_t lds; int slot; };
+struct PlacedShape { PlacedKernel k; uint32_t lds; };
 PlacedShape placed_shape(int elem_size)
 {
   switch (elem_size) {
-  case 1: return {cascaded_compress_placed_kernel<1>, wave_lds_bytes<1>(), 0};
-  case 2: return {cascaded_compress_placed_kernel<2>, wave_lds_bytes<2>(), 1};
-  case 4: return {cascaded_compress_placed_kernel<4>, wave_lds_bytes<4>(), 2};
-  default: return {cascaded_compress_placed_kernel<8>, wave_lds_bytes<8>(), 3};
+  case 1: return {cascaded_compress_placed_kernel<1>, wave_lds_bytes<1>()};
+  case 2: return {cascaded_compress_placed_kernel<2>, wave_lds_bytes<2>()};
+  case 4: return {cascaded_compress_placed_kernel<4>, wave_lds_bytes<4>()};
+  default: return {cascaded_compress_placed_kernel<8>, wave_lds_bytes<8>()};
   }
 }
-// workgroups of the placed kernel the device holds at once (0: could not be found out)
+// workgroups of the placed kernel the current device holds at once (0: could not be found out)
 unsigned placed_resident(int elem_size)
 {
-  static std::atomic<unsigned> known[4]; // (the same on every device of the process)
   const PlacedShape sh = placed_shape(elem_size);
-  unsigned r = known[sh.slot].load(std::memory_order_relaxed);
-  if (r == 0) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sh.k, kWave, sh.lds) != hipSuccess || per_cu <= 0) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    r = (unsigned)per_cu * (unsigned)num_cus_of_current_device();
-    known[sh.slot].store(r, std::memory_order_relaxed);
-  }
-  return r;
+  return (unsigned)resident_per_cu(reinterpret_cast<const void*>(sh.k), kWave, sh.lds)
+         * (unsigned)num_cus_of_current_device();
 }
 } // namespace
 

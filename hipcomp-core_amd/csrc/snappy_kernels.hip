@@ -30,11 +30,10 @@
 // behaviour of the reference is replaced by an error status.
 
 #include "snappy_launch.hpp"
-#include "lz4_launch.hpp" // num_cus_of_current_device
+#include "device_facts.hpp"
 #include "placement.hiph"
 #include "wave_utils.hpp"
 
-#include <atomic>
 
 namespace hcamd {
 
@@ -997,20 +996,12 @@ void snappy_launch_compress(
 }
 
 namespace {
+// workgroups of the placed kernel for `batch` chunks: no more than the current device holds at once (0: could not
+// be found out)
 unsigned placed_grid(size_t batch)
 {
-  static std::atomic<unsigned> known{0}; // (the same on every device of the process)
-  unsigned resident = known.load(std::memory_order_relaxed);
-  if (resident == 0) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, snappy_compress_placed_kernel, kWave, 0) != hipSuccess
-        || per_cu <= 0) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    resident = (unsigned)per_cu * (unsigned)num_cus_of_current_device();
-    known.store(resident, std::memory_order_relaxed);
-  }
+  const unsigned resident = (unsigned)resident_per_cu(reinterpret_cast<const void*>(snappy_compress_placed_kernel), kWave, 0)
+                            * (unsigned)num_cus_of_current_device();
   return batch < resident ? (unsigned)batch : resident;
 }
 } // namespace
