@@ -49,13 +49,7 @@ namespace {
 // throughput, eight more decompress launches -- measured useless and removed in round 4.)
 constexpr uint32_t kPartMeta = 8;
 constexpr uint32_t CB = 4096;
-#ifndef HC_CASC_STOP_AFTER
-#define HC_CASC_STOP_AFTER 0 // (measurement builds only: see the encoder's fast path)
-#endif
-#ifndef HC_CASC_WAVES
-#define HC_CASC_WAVES 1 // 6 KiB of LDS per wave: separate blocks pack 25 per CU
-#endif
-constexpr int kWavesPerBlock = HC_CASC_WAVES;
+constexpr int kWavesPerBlock = 1; // 6 KiB of LDS per wave: separate blocks pack 25 per CU
 
 template <int S> struct UIntOf;
 template <> struct UIntOf<1> { typedef uint8_t type; typedef int8_t stype; };
@@ -891,9 +885,6 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
   UT* bufA = reinterpret_cast<UT*>(my);
   uint16_t* cnts = reinterpret_cast<uint16_t*>(my + enc_buf_bytes());                       // (the generic path's layout)
   uint32_t* meta = reinterpret_cast<uint32_t*>(my + enc_buf_bytes() + (CB / S) * 2);
-  (void)bufA;
-  (void)cnts;
-  (void)meta;
   if (in == nullptr || in_bytes64 == 0) // reference :856-860
     return 0;
   const uint32_t in_bytes = (uint32_t)in_bytes64;
@@ -909,7 +900,6 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
 
   if constexpr (S == 4) {
     // ---- the fast path (see rle16 / write_array4 above)
-    static_assert(kWavesPerBlock == 1 || true, "");
     uint8_t* const X = my;
     uint8_t* const Eb = my + kX4Bytes;
     for (uint32_t c = 0; c < nchunks && use; ++c) {
@@ -922,20 +912,6 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
         load16_global_full(in + (size_t)c * CB, v, lane);
       else
         load16_global(in + (size_t)c * CB, n, v, lane);
-      // (measurement builds, scripts/pmc_cascaded_stages.sh: a sub-chunk is left behind stage HC_CASC_STOP_AFTER --
-      // 1 RLE, 2 its lengths packed, 3 delta, 4 the second RLE, 5 its lengths packed -- and the counters of two such
-      // builds differ by what the stage between them executes; the output is then not a stream)
-#if HC_CASC_STOP_AFTER
-      int stage = 0;
-#define HC_STAGE_DONE()                       \
-  if (++stage == HC_CASC_STOP_AFTER) {        \
-    cut_short = true;                         \
-    break;                                    \
-  }
-      bool cut_short = false;
-#else
-#define HC_STAGE_DONE()
-#endif
       // (Touching the next sub-chunk's lines here, so that its loads hit the L2 -- a wave meets the HBM's
       // latency 16 times per partition -- made the kernel slower, 1958 -> 1825 GB/s: it is not what the
       // waves wait for.)
@@ -949,7 +925,6 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
 #pragma unroll
           for (int k = 0; k < 16; ++k)
             v[k] = 0; // (the registers are free from here on: what comes next loads its own)
-          HC_STAGE_DONE()
           const uint32_t ob = write_array4<true>(out, cur, limit, X, Eb, m, bp, lane);
           if (ob == 0xFFFFFFFFu) {
             use = false;
@@ -960,7 +935,6 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
           n = m;
           --rr;
           in_regs = false;
-          HC_STAGE_DONE()
         }
         if (dr > 0) { // reference :955-977
           if (n == 0) { // undefined in the reference (:323); raw fallback here
@@ -975,22 +949,10 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
           n -= 1;
           --dr;
           in_regs = true;
-          HC_STAGE_DONE()
         }
       }
-#undef HC_STAGE_DONE
       if (!use)
         break;
-#if HC_CASC_STOP_AFTER
-      if (cut_short) {
-        if (in_regs) { // (what the stage left in registers counts as used)
-#pragma unroll
-          for (int k = 0; k < 16; ++k)
-            asm volatile("" ::"v"(v[k]));
-        }
-        continue;
-      }
-#endif
       if (in_regs)
         store16_lds(X, n, v, lane);
 #pragma unroll
@@ -1106,12 +1068,10 @@ __device__ __forceinline__ uint32_t cascaded_encode_partition(
   return total;
 }
 
-// (launch bound: HC_CASC_OCC waves per SIMD; LDS allows 25 one-wave workgroups per CU)
-#ifndef HC_CASC_OCC
-#define HC_CASC_OCC 6
-#endif
+// (launch bound: kCompressOcc waves per SIMD; LDS allows 25 one-wave workgroups per CU)
+constexpr int kCompressOcc = 6;
 template <int S>
-__global__ __launch_bounds__(kWave * kWavesPerBlock, HC_CASC_OCC) void cascaded_compress_kernel(
+__global__ __launch_bounds__(kWave * kWavesPerBlock, kCompressOcc) void cascaded_compress_kernel(
     const uint8_t* const* __restrict__ in_ptrs,
     const size_t* __restrict__ in_bytes_arr,
     uint8_t* const* __restrict__ out_ptrs,
@@ -1139,7 +1099,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, HC_CASC_OCC) void cascaded_
 // wave's slot and moved to its place in the container.
 // (5 waves per SIMD instead of 6, no spills: 1 990 -> 1 915 GB/s)
 template <int S>
-__global__ __launch_bounds__(kWave, HC_CASC_OCC) void cascaded_compress_placed_kernel(
+__global__ __launch_bounds__(kWave, kCompressOcc) void cascaded_compress_placed_kernel(
     const uint8_t* const* __restrict__ in_ptrs, const size_t* __restrict__ in_bytes_arr,
     size_t* __restrict__ out_bytes_arr, const uint32_t batch, const int type_tag, const int R, const int D, const int bp,
     uint32_t* __restrict__ ticket, const Placement place)
@@ -1614,11 +1574,8 @@ __device__ __forceinline__ void cascaded_decode_partition4(
 
 // (launch bound: 4 waves per SIMD where LDS lets a CU hold 14 of these one-wave workgroups, 5 for the
 // 4-byte fast path, which holds 21)
-#ifndef HC_CASC_DEC_OCC
-#define HC_CASC_DEC_OCC 5
-#endif
 template <int S>
-__global__ __launch_bounds__(kWave, S == 4 ? HC_CASC_DEC_OCC : 4) void cascaded_decompress_kernel(
+__global__ __launch_bounds__(kWave, S == 4 ? 5 : 4) void cascaded_decompress_kernel(
     const uint8_t* const* __restrict__ comp_ptrs,
     const size_t* __restrict__ comp_bytes_arr,
     const size_t* __restrict__ out_caps, const size_t batch,
@@ -1990,7 +1947,6 @@ __device__ __forceinline__ void cascaded_decode_partition4(
       // sub-chunk -> output (outputs are 4-byte aligned: cascaded.h:178-193): four consecutive elements
       // per lane and step (they lie in one block of the padded layout), 1 KiB per store instruction
       HC_GLOBAL uint32_t* dst = reinterpret_cast<HC_GLOBAL uint32_t*>(out + (size_t)done * S);
-#ifndef HC_CASC_DEC_LATE_WAIT
       // The words of the next sub-chunk, asked for at the top of this one, are here by now: have them
       // waited for HERE, in front of this sub-chunk's stores.  Vector memory operations are counted in
       // order, and a wait at the top of the next sub-chunk -- behind the stores -- is a wait for the
@@ -1998,7 +1954,6 @@ __device__ __forceinline__ void cascaded_decode_partition4(
 #pragma unroll
       for (int k = 0; k < (int)kStagePerLane; ++k)
         asm volatile("" : "+v"(pf[k]));
-#endif
       if (n == (int)CE) { // a full sub-chunk (all but a partition's last one): no tests, one address, immediate steps
         const uint8_t* px0 = X + x4_addr(4u * (uint32_t)lane);
         HC_GLOBAL uint32_t* d0 = dst + 4u * (uint32_t)lane;

@@ -40,16 +40,10 @@ constexpr uint32_t kPairSyncBytes = 64; // (48 .. 63: the diagnostic build's two
 // LDS-table wave (u16 each; 512 per wave in full workgroups), lanes a trip of the lean form looks up.
 constexpr int kFarMaxWavesPerGroup = 16;
 constexpr uint32_t kFarScratchSlots = 2048;
-#ifndef HC_FAR_SPAN
-#define HC_FAR_SPAN 40 // (measurement builds; bytes, 20 000 chunks: 32: harness 88 / text 38.5 GB/s, 40: 97 / 38.6, 48: 99.5 / 37.2)
-#endif
-constexpr int kFarSpan = HC_FAR_SPAN;
+constexpr int kFarSpan = 40; // (bytes, 20 000 chunks: 32: harness 88 / text 38.5 GB/s, 40: 97 / 38.6, 48: 99.5 / 37.2)
 constexpr int kFarSpanFull = 64; // (all lanes: the words behind the window, far_straight_several: `ext`)
 
 // Decoder waves per workgroup (lz4_decode.hiph: why four)
-#ifndef HC_DEC_WAVES
-#define HC_DEC_WAVES 4
-#endif
-constexpr int kDecompWavesPerBlock = HC_DEC_WAVES;
+constexpr int kDecompWavesPerBlock = 4;
 
 } // namespace hcamd

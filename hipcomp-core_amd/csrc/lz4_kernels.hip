@@ -189,29 +189,6 @@ Lz4Overrides lz4_overrides() { return Lz4Overrides(); }
 } // namespace
 #endif
 
-#ifdef HC_TRIP_STATS
-// (measurement build only; the name makes it pass the export map)
-extern "C" int hipcompBatchedLZ4DebugTripStats(uint32_t* host16, int reset)
-{
-  uint32_t zeros[16] = {};
-  if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_trip_stats), sizeof(zeros)) != hipSuccess)
-    return 1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_trip_stats), zeros, sizeof(zeros)) != hipSuccess)
-    return 2;
-  return 0;
-}
-extern "C" int hipcompBatchedLZ4DebugTripLog(uint32_t* host_words, uint32_t* count, int reset)
-{
-  if (hipMemcpyFromSymbol(count, HIP_SYMBOL(g_trip_log_n), 4) != hipSuccess
-      || hipMemcpyFromSymbol(host_words, HIP_SYMBOL(g_trip_log), 4u << 16) != hipSuccess)
-    return 1;
-  uint32_t zero = 0;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_trip_log_n), &zero, 4) != hipSuccess)
-    return 2;
-  return 0;
-}
-#endif
-
 #ifdef HC_PAIR_DEBUG
 // (diagnostic build only; the name makes it pass the export map)
 extern "C" int hipcompBatchedLZ4DebugPair(uint32_t* host16, int reset)
@@ -220,32 +197,6 @@ extern "C" int hipcompBatchedLZ4DebugPair(uint32_t* host16, int reset)
   if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_pair_dbg), sizeof(zeros)) != hipSuccess)
     return 1;
   if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_pair_dbg), zeros, sizeof(zeros)) != hipSuccess)
-    return 2;
-  return 0;
-}
-#endif
-
-#ifdef HC_MIX_STAMPS
-// (diagnostic build only; the name makes it pass the export map)
-extern "C" int hipcompBatchedLZ4DebugMixStamps(unsigned long long* host8, int reset)
-{
-  unsigned long long zeros[8] = {};
-  if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(g_mix_stamps), sizeof(zeros)) != hipSuccess)
-    return 1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_mix_stamps), zeros, sizeof(zeros)) != hipSuccess)
-    return 2;
-  return 0;
-}
-#endif
-
-#ifdef HC_DEC_STAMPS
-// (diagnostic build only; the name makes it pass the export map)
-extern "C" int hipcompBatchedLZ4DebugDecodeStamps(unsigned long long* host8, int reset)
-{
-  unsigned long long zeros[8] = {};
-  if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(g_dec_stamps), sizeof(zeros)) != hipSuccess)
-    return 1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_dec_stamps), zeros, sizeof(zeros)) != hipSuccess)
     return 2;
   return 0;
 }

@@ -57,11 +57,7 @@ void set_groups(MixShape& sh, size_t batch, uint32_t cus)
 MixShape mix_shape(uint32_t ht_size, size_t batch, uint32_t cus)
 {
   MixShape sh;
-#ifdef HC_TAG_HALF
-  sh.stride_tagged = round_up(ht_size * 2u + ht_size / 2u, 16u);
-#else
   sh.stride_tagged = round_up(ht_size * 3u, 16u);
-#endif
   sh.stride_plain = round_up(ht_size * 2u, 16u);
   // most waves per CU first (workgroups of g waves, as many as fit), then
   // most of them with tags

@@ -71,10 +71,7 @@ constexpr uint32_t kStraightMargin = 64 + 8 + 64 + 8;
 // lanes whose candidates one trip of the straight path fetches; it looks at the
 // words of lanes 0..kSpan+11, which come from the window before if the elements
 // moved on by no more than kStraightReach bytes
-#ifndef HC_SNAPPY_SPAN
-#define HC_SNAPPY_SPAN 52 // (measurement builds: 16..52; 32: 71.2, 40: 77.4, 48: 82.7, 52: 84.0 GB/s on text)
-#endif
-constexpr int kSpan = HC_SNAPPY_SPAN;
+constexpr int kSpan = 52; // (measured 16..52; 32: 71.2, 40: 77.4, 48: 82.7, 52: 84.0 GB/s on text)
 // pick() below takes the first event at or above `start` with `start` clamped to lane 63: with an event AT lane
 // 63 and an element that ends beyond lane 63 it would take that same event again and again (an endless loop,
 // met in round 3 with a 64-lane span).  Lanes from kSpan on never report an event, so the span has to stop short

@@ -1,6 +1,6 @@
 """A/B of LZ4 launch shapes / geometries in ONE process on the same buffers (the knobs are read at
 every call): ab_shapes.py --chunks N --dist harness,text --dtype char CONFIG [CONFIG ...]
-CONFIG = SHAPE[:BOTH][@VARIANT] e.g. auto  far  far:4,0,2048  auto:1,7,512  auto:1,3,512@span52 (lib/libhipcomp_span52.so);
+CONFIG = SHAPE[:BOTH][@VARIANT] e.g. auto  far  far:4,0,2048  auto:1,7,512  auto:1,3,512@pairdbg (lib/libhipcomp_pairdbg.so);
 bytes are compared with the first config's."""
 import argparse, importlib, os, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

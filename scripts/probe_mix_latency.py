@@ -9,7 +9,7 @@ import bench
 ap = argparse.ArgumentParser()
 ap.add_argument("--chunks", type=int, default=100000)
 ap.add_argument("--codec", default="lz4", help="lz4 | snappy")
-ap.add_argument("--lib", default=None, help="another build of the library, e.g. hipcomp-core_amd/lib/libhipcomp_smalltab.so (timing-only: no verify)")
+ap.add_argument("--lib", default=None, help="another build of the library, e.g. hipcomp-core_amd/lib/libhipcomp_knobs.so (make VARIANT=knobs)")
 ap.add_argument("--dist", default="uniform", help="uniform | harness | runs | text (the far kernels: candidates come from the same few chunks too)")
 a = ap.parse_args()
 hc = importlib.import_module("hipcomp-core_amd")

@@ -219,3 +219,21 @@ def test_committed_profiles_belong_to_the_build_at_hand():
         "(scripts/collect_profiles.sh) or bench.py reports roofline.traffic = null")
     bench.PROFILED_ROWS = None
     assert bench.profiled("lz4/uniform/char/100000", "compress") is not None
+
+
+def test_kernel_sources_have_no_build_switches_but_the_knobs_and_the_pair_counters():
+    """The shipped form of the kernels is their only form: the sources in csrc/ test no macro but
+    HC_MEASUREMENT_KNOBS (the knobs build, host code only) and HC_PAIR_DEBUG (the pair walk's wait
+    counters).  Tuned values are constexpr; a concluded experiment leaves with its switch."""
+    import glob
+    allowed = {"HC_MEASUREMENT_KNOBS", "HC_PAIR_DEBUG"}
+    directive = re.compile(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*(?:\\\n.*)*)", re.M)
+    named = {}
+    paths = [p for ext in ("hip", "hiph", "hpp", "cpp") for p in glob.glob(os.path.join(CSRC, "*." + ext))]
+    assert len(paths) >= 20
+    for path in paths:
+        for cond in directive.findall(open(path).read()):
+            cond = re.sub(r"//.*|/\*.*?\*/", "", cond)
+            for name in set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}:
+                named.setdefault(name, []).append(os.path.basename(path))
+    assert set(named) <= allowed, {k: v for k, v in named.items() if k not in allowed}
