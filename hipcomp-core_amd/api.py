@@ -39,6 +39,8 @@ class hipcompStatus:
     ErrorInvalidValue = 10
     ErrorNotSupported = 11
     ErrorCannotDecompress = 12
+    ErrorBadChecksum = 13
+    ErrorCannotVerifyChecksums = 14
     ErrorCudaError = 1000
     ErrorInternal = 10000
 

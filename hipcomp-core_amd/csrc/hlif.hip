@@ -15,6 +15,7 @@
 // stream, event or thread of the manager's own: everything runs on the caller's stream.  The scratch space is a
 // constant of the manager, as in the reference.
 #include "cascaded_launch.hpp"
+#include "checksum_launch.hpp"
 #include "host_common.hpp"
 #include "lz4_launch.hpp"
 #include "snappy_launch.hpp"
@@ -247,6 +248,25 @@ struct Core
   hipcompBatchedCascadedOpts_t cascaded_opts = {};
   int cascaded_elem = 4;
 
+  // CRC-32 checksums (checksum_launch.hpp): what compress writes and decompress checks
+  hipcomp::ChecksumPolicy policy = hipcomp::NoComputeNoVerify;
+  bool computes() const
+  {
+    return policy == hipcomp::ComputeAndNoVerify || policy == hipcomp::ComputeAndVerifyIfPresent
+           || policy == hipcomp::ComputeAndVerify;
+  }
+  bool verifies() const
+  {
+    return policy == hipcomp::NoComputeAndVerifyIfPresent || policy == hipcomp::ComputeAndVerifyIfPresent
+           || policy == hipcomp::ComputeAndVerify;
+  }
+  void set_policy(hipcomp::ChecksumPolicy p)
+  {
+    if (p < hipcomp::NoComputeNoVerify || p > hipcomp::ComputeAndVerify)
+      throw std::runtime_error("unknown ChecksumPolicy " + std::to_string((int)p));
+    policy = p;
+  }
+
   uint8_t* scratch = nullptr;
   bool own_scratch = false;
   CommonHeader* header_host = nullptr; // pinned
@@ -297,11 +317,26 @@ struct Core
   {
     return 16 * chunks + 64 + placement_slots() * slot_bytes + 16 + lz4_temp_bytes(chunks);
   }
+  // the checksums of a pass (behind what the pass needs without them, 16-byte aligned): the CrcState, the scan
+  size_t checksum_bytes(size_t chunks) const
+  {
+    return policy == hipcomp::NoComputeNoVerify ? 0 : 16 + 64 + crc_pass_bytes(chunks);
+  }
+  static uint8_t* checksum_area(uint8_t* behind)
+  {
+    return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(behind) + 15) & ~uintptr_t(15));
+  }
+  // bytes of the uncompressed buffer that chunks [first, first + count) cover
+  uint64_t slice_bytes(uint64_t total, size_t first, size_t count) const
+  {
+    const uint64_t end = (uint64_t)(first + count) * chunk_bytes;
+    return (end < total ? end : total) - (uint64_t)first * chunk_bytes;
+  }
   // what a caller's own scratch buffer must hold
   size_t scratch_bytes() const
   {
     const size_t a = placed_scratch_bytes(kPlacedSlab), b = lists_bytes();
-    return a > b ? a : b;
+    return (a > b ? a : b) + checksum_bytes(kPlacedSlab);
   }
   // The manager's own scratch is as large as the calls so far needed (a buffer of a few chunks does not
   // pay for the lists of a full pass); the caller's is scratch_bytes() by contract.
@@ -342,7 +377,7 @@ struct Core
       throw std::runtime_error("CascadedManager::compress: num_RLEs / num_deltas do not fit the 64-byte chunk metadata");
     const size_t n = cfg.num_chunks;
     const size_t per_pass = n < kPlacedSlab ? (n ? n : 1) : kPlacedSlab;
-    uint8_t* const s = ensure_scratch(placed_scratch_bytes(per_pass));
+    uint8_t* const s = ensure_scratch(placed_scratch_bytes(per_pass) + checksum_bytes(per_pass));
     const Layout lay = layout(n);
     const uint8_t** in_ptrs = reinterpret_cast<const uint8_t**>(s);
     size_t* in_bytes = reinterpret_cast<size_t*>(s + per_pass * 8);
@@ -352,6 +387,10 @@ struct Core
         (reinterpret_cast<uintptr_t>(slots + placement_slots() * slot_bytes) + 15) & ~uintptr_t(15));
     header_kernel<<<1, 1, 0, stream>>>(comp_buffer, cfg.uncompressed_buffer_size, n, chunk_bytes, (uint32_t)lay.data,
                                        format, format_header, format_header_bytes, cfg.get_status());
+    uint8_t* const csum = computes() ? checksum_area(s + placed_scratch_bytes(per_pass)) : nullptr;
+    CrcState* const crc_state = reinterpret_cast<CrcState*>(csum);
+    if (csum)
+      check(crc_launch_reset(crc_state, stream), "compress: checksums");
     for (size_t first = 0; first < n; first += per_pass) {
       const uint32_t count = (uint32_t)(n - first < per_pass ? n - first : per_pass);
       slab_inputs_kernel<<<(count + kBlock - 1) / kBlock, kBlock, 0, stream>>>(
@@ -381,7 +420,45 @@ struct Core
               "CascadedManager::compress");
         break;
       }
+      if (csum) {
+        // the input slices (arithmetic places) and the placed chunks (in chunk-index order by the scan of sizes)
+        const uint64_t slice = slice_bytes(cfg.uncompressed_buffer_size, first, count);
+        CrcChunks in;
+        in.ptrs = in_ptrs;
+        in.lens = in_bytes;
+        in.count = count;
+        CrcTarget in_t;
+        in_t.values = reinterpret_cast<uint32_t*>(comp_buffer + lay.decomp_checksums) + first;
+        in_t.stride = chunk_bytes;
+        in_t.pass_bytes = slice;
+        in_t.pass_word = &crc_state->decomp_pass;
+        in_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(in, in_t, stream), "compress: checksums");
+        CrcChunks out;
+        out.base = place.data;
+        out.offsets = place.offsets;
+        out.lens = sizes;
+        out.count = count;
+        uint64_t* const work = reinterpret_cast<uint64_t*>(csum + 64);
+        check(crc_launch_scan(out, work, crc_state, stream), "compress: checksums");
+        CrcTarget out_t;
+        out_t.values = reinterpret_cast<uint32_t*>(comp_buffer + lay.comp_checksums) + first;
+        out_t.before = work;
+        out_t.pass_bytes_dev = &crc_state->comp_pass_bytes;
+        out_t.pass_word = &crc_state->comp_pass;
+        out_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(out, out_t, stream), "compress: checksums");
+        check(crc_launch_fold(crc_state, slice, stream), "compress: checksums");
+      }
     }
+    if (csum)
+      check(crc_launch_finish_compress(
+                reinterpret_cast<uint32_t*>(comp_buffer + offsetof(CommonHeader, full_comp_buffer_checksum)),
+                reinterpret_cast<uint32_t*>(comp_buffer + offsetof(CommonHeader, decomp_buffer_checksum)),
+                reinterpret_cast<bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_comp_buffer_checksums)),
+                reinterpret_cast<bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_decomp_buffer_checksums)),
+                crc_state, stream),
+            "compress: checksums");
     check(hipGetLastError(), "compress kernels");
   }
 
@@ -423,7 +500,7 @@ struct Core
 
   void decompress(uint8_t* decomp_buffer, const uint8_t* comp_buffer, const hipcomp::DecompressionConfig& cfg)
   {
-    uint8_t* const s = ensure_scratch(lists_bytes());
+    uint8_t* const s = ensure_scratch(lists_bytes() + checksum_bytes(slab));
     const size_t n = cfg.num_chunks;
     const Layout lay = layout(n);
     const uint8_t** comp_ptrs = reinterpret_cast<const uint8_t**>(s);
@@ -435,6 +512,16 @@ struct Core
     if (n == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() == hipcompErrorCannotDecompress)
       return;
     set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
+    // the checksums: read exactly what the decoder is given (comp_ptrs, sizes) and what it wrote (out_ptrs,
+    // actual), and only where the container's flags (read on the device) say there are values to compare with
+    uint8_t* const csum = verifies() ? checksum_area(s + lists_bytes()) : nullptr;
+    CrcState* const crc_state = reinterpret_cast<CrcState*>(csum);
+    const bool* const comp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_comp_buffer_checksums));
+    const bool* const decomp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_decomp_buffer_checksums));
+    if (csum)
+      check(crc_launch_reset(crc_state, stream), "decompress: checksums");
     for (size_t first = 0; first < n; first += slab) {
       const uint32_t count = (uint32_t)(n - first < slab ? n - first : slab);
       slab_streams_kernel<<<(count + kBlock - 1) / kBlock, kBlock, 0, stream>>>(
@@ -464,7 +551,46 @@ struct Core
       }
       slab_verdict_kernel<<<(count + kBlock - 1) / kBlock, kBlock, 0, stream>>>(statuses, actual, caps, count,
                                                                                   cfg.get_status());
+      if (csum) {
+        const uint64_t slice = slice_bytes(cfg.decomp_data_size, first, count);
+        CrcChunks in;
+        in.ptrs = comp_ptrs;
+        in.lens = sizes;
+        in.caps = caps;
+        in.count = count;
+        uint64_t* const work = reinterpret_cast<uint64_t*>(csum + 64);
+        check(crc_launch_scan(in, work, crc_state, stream), "decompress: checksums");
+        CrcTarget in_t;
+        in_t.stored = reinterpret_cast<const uint32_t*>(comp_buffer + lay.comp_checksums) + first;
+        in_t.present = comp_flag;
+        in_t.before = work;
+        in_t.pass_bytes_dev = &crc_state->comp_pass_bytes;
+        in_t.pass_word = &crc_state->comp_pass;
+        in_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(in, in_t, stream), "decompress: checksums");
+        CrcChunks out;
+        out.ptrs = out_ptrs;
+        out.lens = actual;
+        out.caps = caps;
+        out.clamp_to_caps = true;
+        out.count = count;
+        CrcTarget out_t;
+        out_t.stored = reinterpret_cast<const uint32_t*>(comp_buffer + lay.decomp_checksums) + first;
+        out_t.present = decomp_flag;
+        out_t.stride = chunk_bytes;
+        out_t.pass_bytes = slice;
+        out_t.pass_word = &crc_state->decomp_pass;
+        out_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(out, out_t, stream), "decompress: checksums");
+        check(crc_launch_fold(crc_state, slice, stream), "decompress: checksums");
+      }
     }
+    if (csum)
+      check(crc_launch_finish_decompress(
+                reinterpret_cast<const uint32_t*>(comp_buffer + offsetof(CommonHeader, full_comp_buffer_checksum)),
+                reinterpret_cast<const uint32_t*>(comp_buffer + offsetof(CommonHeader, decomp_buffer_checksum)),
+                comp_flag, decomp_flag, crc_state, policy == hipcomp::ComputeAndVerify, cfg.get_status(), stream),
+            "decompress: checksums");
     check(hipGetLastError(), "decompress kernels");
   }
 
@@ -565,6 +691,12 @@ LZ4Manager::LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStr
   m.ht_size = (uint32_t)(p < 16384 ? p : 16384);
   m.finish_init(slot);
 }
+LZ4Manager::LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStream_t user_stream, const int device_id,
+                       ChecksumPolicy checksum_policy)
+    : LZ4Manager(uncomp_chunk_size, data_type, user_stream, device_id)
+{
+  impl->core.set_policy(checksum_policy);
+}
 HCAMD_MANAGER_METHODS(LZ4Manager)
 
 SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, int device_id)
@@ -579,6 +711,11 @@ SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, 
   m.format = kSnappy;
   m.format_header_bytes = sizeof(SnappyFormatSpecHeader); // 1: an empty struct
   m.finish_init(slot);
+}
+SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, int device_id, ChecksumPolicy checksum_policy)
+    : SnappyManager(uncomp_chunk_size, user_stream, device_id)
+{
+  impl->core.set_policy(checksum_policy);
 }
 HCAMD_MANAGER_METHODS(SnappyManager)
 
@@ -614,10 +751,22 @@ CascadedManager::CascadedManager(const hipcompBatchedCascadedOpts_t& options, hi
   m.place_align = 8;
   m.finish_init(slot);
 }
+CascadedManager::CascadedManager(const hipcompBatchedCascadedOpts_t& options, hipStream_t user_stream, int device_id,
+                                 ChecksumPolicy checksum_policy)
+    : CascadedManager(options, user_stream, device_id)
+{
+  impl->core.set_policy(checksum_policy);
+}
 HCAMD_MANAGER_METHODS(CascadedManager)
 
 // reference hipcompManagerFactory.cpp:44-148 (synchronises the stream, as there)
 std::shared_ptr<hipcompManagerBase> create_manager(const uint8_t* comp_buffer, hipStream_t stream, const int device_id)
+{
+  return create_manager(comp_buffer, stream, device_id, NoComputeNoVerify);
+}
+
+std::shared_ptr<hipcompManagerBase> create_manager(
+    const uint8_t* comp_buffer, hipStream_t stream, const int device_id, ChecksumPolicy checksum_policy)
 {
   struct Heads
   {
@@ -630,16 +779,17 @@ std::shared_ptr<hipcompManagerBase> create_manager(const uint8_t* comp_buffer, h
   case kLZ4: {
     uint32_t t;
     std::memcpy(&t, heads.format.bytes, sizeof(t));
-    return std::make_shared<LZ4Manager>((size_t)heads.common.uncomp_chunk_size, (hipcompType_t)t, stream, device_id);
+    return std::make_shared<LZ4Manager>((size_t)heads.common.uncomp_chunk_size, (hipcompType_t)t, stream, device_id,
+                                        checksum_policy);
   }
   case kSnappy:
-    return std::make_shared<SnappyManager>((size_t)heads.common.uncomp_chunk_size, stream, device_id);
+    return std::make_shared<SnappyManager>((size_t)heads.common.uncomp_chunk_size, stream, device_id, checksum_policy);
   case kCascaded: {
     hipcompBatchedCascadedOpts_t o;
     std::memcpy(&o, heads.format.bytes, sizeof(o));
     if (o.chunk_size != heads.common.uncomp_chunk_size)
       throw std::runtime_error("create_manager: Cascaded options do not match the container's chunk size");
-    return std::make_shared<CascadedManager>(o, stream, device_id);
+    return std::make_shared<CascadedManager>(o, stream, device_id, checksum_policy);
   }
   default:
     throw std::runtime_error("create_manager: format " + std::to_string((int)heads.common.format)

@@ -25,6 +25,8 @@ struct CascadedManager : hipcompManagerBase
   CascadedManager(
       const hipcompBatchedCascadedOpts_t& options = hipcompBatchedCascadedDefaultOpts, hipStream_t user_stream = 0,
       int device_id = 0);
+  CascadedManager(const hipcompBatchedCascadedOpts_t& options, hipStream_t user_stream, int device_id,
+                  ChecksumPolicy checksum_policy);
   ~CascadedManager() override;
   CascadedManager(const CascadedManager&) = delete;
   CascadedManager& operator=(const CascadedManager&) = delete;

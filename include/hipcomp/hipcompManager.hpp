@@ -10,7 +10,7 @@
  * the other way round:
  *
  *   CommonHeader (64 B) | format header | pad to 8 | chunk offsets u64 x n |
- *   chunk sizes u64 x n | 2 x checksums u32 x n (unused, as in the reference) | chunk data
+ *   chunk sizes u64 x n | 2 x checksums u32 x n (zero unless a ChecksumPolicy computes them) | chunk data
  *
  * Behind it are the batched codecs of this library (the chunks of a container are exactly
  * the streams hipcompBatched*CompressAsync produces).  Differences by design: chunk data
@@ -30,6 +30,21 @@
 
 namespace hipcomp
 {
+
+/* What a manager does with the CRC-32 checksums of its containers (nvCOMP 3's names; INTEGRATION.md says what
+   each checksum covers).  Compute*: compress fills the header's two full checksums and both per-chunk arrays
+   and sets both include_per_chunk_* flags.  *Verify*: decompress checks what the container's flags say is
+   present and reports hipcompErrorBadChecksum when a stored value differs; ComputeAndVerify also reports
+   hipcompErrorCannotVerifyChecksums when a flag is false.  The constructors without a policy mean
+   NoComputeNoVerify: containers as the reference writes them (zeros, false), nothing checked. */
+enum ChecksumPolicy
+{
+  NoComputeNoVerify,
+  ComputeAndNoVerify,
+  NoComputeAndVerifyIfPresent,
+  ComputeAndVerifyIfPresent,
+  ComputeAndVerify
+};
 
 struct CompressionConfig
 {
@@ -62,7 +77,8 @@ struct hipcompManagerBase
   virtual CompressionConfig configure_compression(const size_t decomp_buffer_size) = 0;
   /* asynchronous on the manager's stream; both buffers device-accessible */
   virtual void compress(const uint8_t* decomp_buffer, uint8_t* comp_buffer, const CompressionConfig& comp_config) = 0;
-  /* reads the container's header (synchronises the stream) */
+  /* reads the container's header (synchronises the stream); the status (after decompress) is
+     hipcompErrorBadChecksum > hipcompErrorCannotDecompress > hipcompErrorCannotVerifyChecksums > hipcompSuccess */
   virtual DecompressionConfig configure_decompression(const uint8_t* comp_buffer) = 0;
   /* from the config the buffer was compressed with (no synchronisation) */
   virtual DecompressionConfig configure_decompression(const CompressionConfig& comp_config) = 0;

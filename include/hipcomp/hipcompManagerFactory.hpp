@@ -18,6 +18,9 @@ namespace hipcomp
 
 std::shared_ptr<hipcompManagerBase> create_manager(
     const uint8_t* comp_buffer, hipStream_t stream = 0, const int device_id = 0);
+/* the same, with the manager's checksum policy (hipcompManager.hpp) */
+std::shared_ptr<hipcompManagerBase> create_manager(
+    const uint8_t* comp_buffer, hipStream_t stream, const int device_id, ChecksumPolicy checksum_policy);
 
 } // namespace hipcomp
 

@@ -20,6 +20,8 @@ struct LZ4Manager : hipcompManagerBase
 {
   /* uncomp_chunk_size at most 16 MiB (the LZ4 block limit); device_id must be the current device */
   LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStream_t user_stream = 0, const int device_id = 0);
+  LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStream_t user_stream, const int device_id,
+             ChecksumPolicy checksum_policy);
   ~LZ4Manager() override;
   LZ4Manager(const LZ4Manager&) = delete;
   LZ4Manager& operator=(const LZ4Manager&) = delete;

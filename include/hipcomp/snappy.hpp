@@ -20,6 +20,7 @@ struct SnappyManager : hipcompManagerBase
 {
   /* device_id must be the current device */
   SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream = 0, int device_id = 0);
+  SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, int device_id, ChecksumPolicy checksum_policy);
   ~SnappyManager() override;
   SnappyManager(const SnappyManager&) = delete;
   SnappyManager& operator=(const SnappyManager&) = delete;
