@@ -16,8 +16,10 @@
 // constant of the manager, as in the reference.
 #include "cascaded_launch.hpp"
 #include "checksum_launch.hpp"
+#include "hlif_container.hpp"
 #include "host_common.hpp"
 #include "lz4_launch.hpp"
+#include "range_launch.hpp"
 #include "snappy_launch.hpp"
 #include "wave_utils.hpp"
 
@@ -39,31 +41,6 @@
 
 namespace hcamd {
 namespace hlif {
-
-// reference src/hipcomp_common_deps/hlif_shared_types.hpp:58-84 (layout by the C++ ABI: 64 bytes)
-enum FormatType : uint8_t { kLZ4 = 0, kSnappy = 1, kANS = 2, kGDeflate = 3, kCascaded = 4, kBitcomp = 5 };
-struct CommonHeader
-{
-  uint32_t magic_number;
-  uint8_t major_version;
-  uint8_t minor_version;
-  uint8_t format;
-  uint64_t comp_data_size;
-  uint64_t decomp_data_size;
-  uint64_t num_chunks;
-  bool include_chunk_starts;
-  uint32_t full_comp_buffer_checksum;
-  uint32_t decomp_buffer_checksum;
-  bool include_per_chunk_comp_buffer_checksums;
-  bool include_per_chunk_decomp_buffer_checksums;
-  uint64_t uncomp_chunk_size;
-  uint32_t comp_data_offset;
-};
-static_assert(sizeof(CommonHeader) == 64, "container header layout");
-static_assert(offsetof(CommonHeader, comp_data_size) == 8 && offsetof(CommonHeader, num_chunks) == 24
-                  && offsetof(CommonHeader, full_comp_buffer_checksum) == 36
-                  && offsetof(CommonHeader, uncomp_chunk_size) == 48 && offsetof(CommonHeader, comp_data_offset) == 56,
-              "container header layout");
 
 // format headers behind the common one (reference include/hipcomp/{lz4,snappy,cascaded}.hpp):
 // LZ4 {hipcompType_t} 4 bytes, Snappy {} 1 byte (an empty struct), Cascaded {options} 24 bytes
@@ -594,6 +571,151 @@ struct Core
     check(hipGetLastError(), "decompress kernels");
   }
 
+  // ---- a ranged read: bytes [first_byte, first_byte + num_bytes) of the buffer into out[0, num_bytes) ----
+  // The plan is range_plan.hpp's.  Only the chunks the range touches are listed, decoded and (under a verifying
+  // policy) checked; a chunk wholly inside the range is decoded straight into out, an edge chunk whole into a
+  // scratch slot from which range_slices_kernel moves the wanted span.  The scratch of such a call, carved out of
+  // what scratch_bytes() promises (the compress slots and lists lie idle meanwhile): the slots (16-byte aligned,
+  // range_slot_stride() each: 2 of them, or one per chunk of a pass where the Cascaded decoder's alignment
+  // contract makes every chunk an edge chunk), the pass's chunk lists and the LZ4 decoder's 64 bytes, the CrcState.
+  size_t range_slot_stride() const { return (chunk_bytes + 15) & ~size_t(15); }
+  static constexpr size_t kRangeFixedBytes = 16 + 64 + 16 + 16 + 64; // alignment, ticket words, alignment x 2, CrcState
+  // what the manager's own scratch holds for ranged reads (a constant: no allocation after the first call)
+  size_t range_own_bytes() const
+  {
+    const size_t want = kRangeFixedBytes + (size_t)slab * 44 + (codec == Cascaded ? 1024 : 2) * range_slot_stride();
+    const size_t all = scratch_bytes();
+    return want < all ? want : all;
+  }
+
+  void decompress_range(uint8_t* out, const uint8_t* comp_buffer, const hipcomp::DecompressionConfig& cfg,
+                        size_t first_byte, size_t num_bytes)
+  {
+    // (a configuration refused by configure_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() == hipcompErrorCannotDecompress)
+      return;
+    const size_t stride = range_slot_stride();
+    const size_t room = scratch && !own_scratch ? scratch_bytes() : range_own_bytes();
+    // chunks per pass with two slots, and with a slot per chunk
+    const size_t fixed = kRangeFixedBytes;
+    size_t two = room > fixed + 2 * stride ? (room - fixed - 2 * stride) / 44 : 0;
+    size_t each = room > fixed ? (room - fixed) / (stride + 44) : 0;
+    two = two < slab ? two : slab;
+    each = each < two ? each : two;
+    if (two < 2)
+      throw std::runtime_error("decompress_range: the scratch space does not hold two chunks of this size");
+    const uint32_t elem = codec == Cascaded ? (uint32_t)cascaded_elem : 1u;
+    // (hipcomp/cascaded.h: buffers 4-byte aligned and aligned to the element type)
+    const uint32_t align = codec == Cascaded ? (elem > 4 ? elem : 4u) : 1u;
+    range::Plan plan;
+    if (!range::range_plan(plan, cfg.decomp_data_size, chunk_bytes, first_byte, num_bytes, (uint32_t)two,
+                           (uint32_t)(each < 2 ? 2 : each), align, (uint32_t)(reinterpret_cast<uintptr_t>(out) % align),
+                           elem)) {
+      set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
+      check(hipGetLastError(), "decompress_range kernels");
+      return;
+    }
+    set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
+    if (plan.chunks == 0) {
+      check(hipGetLastError(), "decompress_range kernels");
+      return;
+    }
+    uint8_t* const s = ensure_scratch(room);
+    const size_t n = cfg.num_chunks;
+    const Layout lay = layout(n);
+    const size_t per_pass = plan.chunks < plan.per_pass ? (size_t)plan.chunks : plan.per_pass;
+    RangeSlots slots;
+    slots.base = checksum_area(s);
+    slots.stride = stride;
+    uint8_t* const lists = slots.base + (plan.all_edge ? per_pass : 2) * stride;
+    const uint8_t** comp_ptrs = reinterpret_cast<const uint8_t**>(lists);
+    size_t* caps = reinterpret_cast<size_t*>(lists + per_pass * 8);
+    uint8_t** out_ptrs = reinterpret_cast<uint8_t**>(lists + per_pass * 16);
+    size_t* actual = reinterpret_cast<size_t*>(lists + per_pass * 24);
+    hipcompStatus_t* statuses = reinterpret_cast<hipcompStatus_t*>(lists + per_pass * 32);
+    uint8_t* const ticket = checksum_area(lists + per_pass * 36); // (the LZ4 decoder's chunk ticket counter: 64 bytes)
+    CrcState* const crc_state = verifies() ? reinterpret_cast<CrcState*>(checksum_area(ticket + 64)) : nullptr;
+    const bool* const comp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_comp_buffer_checksums));
+    const bool* const decomp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_decomp_buffer_checksums));
+    if (crc_state)
+      check(crc_launch_reset(crc_state, stream), "decompress_range: checksums");
+    RangeContainer rc;
+    rc.container = comp_buffer;
+    rc.offsets_at = lay.offsets;
+    rc.data_at = lay.data;
+    rc.num_chunks = n;
+    rc.format = format;
+    for (uint64_t k = 0; k < plan.passes; ++k) {
+      const uint64_t first = range::range_pass_first(plan, k);
+      const uint32_t count = range::range_pass_count(plan, k);
+      check(range_launch_list(rc, plan, first, count, out, slots, comp_ptrs, out_ptrs, caps, cfg.get_status(), stream),
+            "decompress_range: chunk list");
+      const size_t* sizes = reinterpret_cast<const size_t*>(comp_buffer + lay.sizes) + first;
+      switch (codec) {
+      case LZ4:
+        check(lz4_launch_decompress(comp_ptrs, sizes, caps, count, out_ptrs, actual, statuses, true, stream, ticket, 64),
+              "LZ4Manager::decompress_range");
+        break;
+      case Snappy:
+        if (hipcompBatchedSnappyDecompressAsync(reinterpret_cast<const void* const*>(comp_ptrs), sizes, caps, actual, count,
+                                                nullptr, 0, reinterpret_cast<void* const*>(out_ptrs), statuses, stream)
+            != hipcompSuccess)
+          throw std::runtime_error("SnappyManager::decompress_range: batched decompress failed");
+        break;
+      case Cascaded:
+        if (hipcompBatchedCascadedDecompressAsync(reinterpret_cast<const void* const*>(comp_ptrs), sizes, caps, actual,
+                                                  count, nullptr, 0, reinterpret_cast<void* const*>(out_ptrs), statuses,
+                                                  stream)
+            != hipcompSuccess)
+          throw std::runtime_error("CascadedManager::decompress_range: batched decompress failed");
+        break;
+      }
+      slab_verdict_kernel<<<(count + kBlock - 1) / kBlock, kBlock, 0, stream>>>(statuses, actual, caps, count,
+                                                                                  cfg.get_status());
+      if (crc_state) {
+        // per chunk only: the pass words the CRC kernel also keeps (for the full-buffer checksums, which a partial
+        // read cannot check) are not looked at, so no scan of the sizes and no fold
+        CrcChunks in;
+        in.ptrs = comp_ptrs;
+        in.lens = sizes;
+        in.caps = caps;
+        in.count = count;
+        CrcTarget in_t;
+        in_t.stored = reinterpret_cast<const uint32_t*>(comp_buffer + lay.comp_checksums) + first;
+        in_t.present = comp_flag;
+        in_t.pass_bytes = slot_bytes;
+        in_t.pass_word = &crc_state->comp_pass;
+        in_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(in, in_t, stream), "decompress_range: checksums");
+        CrcChunks dec;
+        dec.ptrs = out_ptrs;
+        dec.lens = actual;
+        dec.caps = caps;
+        dec.clamp_to_caps = true;
+        dec.count = count;
+        CrcTarget dec_t;
+        dec_t.stored = reinterpret_cast<const uint32_t*>(comp_buffer + lay.decomp_checksums) + first;
+        dec_t.present = decomp_flag;
+        dec_t.stride = chunk_bytes;
+        dec_t.pass_bytes = (uint64_t)count * chunk_bytes;
+        dec_t.pass_word = &crc_state->decomp_pass;
+        dec_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(dec, dec_t, stream), "decompress_range: checksums");
+      }
+      // (where only the range's ends are edge chunks, they are in the first and in the last pass)
+      if (plan.all_edge || k == 0 || k + 1 == plan.passes)
+        check(range_launch_slices(plan, first, count, out, slots, statuses, actual, caps, stream),
+              "decompress_range: slices");
+    }
+    if (crc_state)
+      check(range_launch_finish(comp_flag, decomp_flag, crc_state, policy == hipcomp::ComputeAndVerify, cfg.get_status(),
+                                stream),
+            "decompress_range: checksums");
+    check(hipGetLastError(), "decompress_range kernels");
+  }
+
   void set_scratch_buffer(uint8_t* new_scratch_buffer)
   {
     if (own_scratch)
@@ -644,7 +766,12 @@ hipcompStatus_t* DecompressionConfig::get_status() const { return status.get(); 
   void M::decompress(uint8_t* out, const uint8_t* comp, const DecompressionConfig& c) { impl->core.decompress(out, comp, c); } \
   void M::set_scratch_buffer(uint8_t* p) { impl->core.set_scratch_buffer(p); }                                      \
   size_t M::get_required_scratch_buffer_size() { return impl->core.scratch_bytes(); }                               \
-  size_t M::get_compressed_output_size(uint8_t* comp) { return impl->core.compressed_output_size(comp); }
+  size_t M::get_compressed_output_size(uint8_t* comp) { return impl->core.compressed_output_size(comp); }                         \
+  void M::decompress_range(uint8_t* out, const uint8_t* comp, const DecompressionConfig& c, size_t first_byte,      \
+                           size_t num_bytes)                                                                        \
+  {                                                                                                                 \
+    impl->core.decompress_range(out, comp, c, first_byte, num_bytes);                                               \
+  }
 
 struct LZ4Manager::Impl
 {

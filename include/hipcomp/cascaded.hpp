@@ -39,6 +39,10 @@ struct CascadedManager : hipcompManagerBase
   void set_scratch_buffer(uint8_t* new_scratch_buffer) override;
   size_t get_required_scratch_buffer_size() override;
   size_t get_compressed_output_size(uint8_t* comp_buffer) override;
+  /* bytes [first_byte, first_byte + num_bytes) of the uncompressed buffer into out[0, num_bytes): only the chunks
+     the range touches are read, decoded and checked (hipcompManager.hpp, "Ranged reads") */
+  void decompress_range(uint8_t* out, const uint8_t* comp_buffer, const DecompressionConfig& decomp_config,
+                        size_t first_byte, size_t num_bytes);
 
 private:
   struct Impl;

@@ -17,6 +17,22 @@
  * lies in chunk order (the reference places chunks in completion order; both record the
  * offsets), configs own their status word instead of borrowing it from a pool, and
  * max_compressed_buffer_size counts the size array at its true width.
+ *
+ * Ranged reads.  The three managers (lz4.hpp, snappy.hpp, cascaded.hpp) also have a non-virtual
+ *
+ *   void decompress_range(uint8_t* out, const uint8_t* comp_buffer, const DecompressionConfig& cfg,
+ *                         size_t first_byte, size_t num_bytes);
+ *
+ * which writes bytes [first_byte, first_byte + num_bytes) of the uncompressed buffer to out[0, num_bytes) and
+ * no byte outside that span, at any alignment of out.  cfg comes from either configure_decompression.  Like
+ * decompress it is asynchronous on the manager's stream and leaves its status in cfg.get_status():
+ * hipcompErrorInvalidValue when first_byte + num_bytes overflows or exceeds cfg.decomp_data_size (CascadedManager:
+ * also when either is not a multiple of the element size) -- nothing else is launched --, otherwise decompress's
+ * BadChecksum > CannotDecompress > CannotVerifyChecksums > Success.  Only the chunks the range touches are read,
+ * decoded and, under a verifying policy, checked against their per-chunk checksums (the chunks at the range's ends
+ * are decoded whole into scratch space, so they are checked too); the two full-buffer checksums are not checked.
+ * A chunk that fails leaves its part of out as it was.  The scratch space is the manager's
+ * (get_required_scratch_buffer_size() is what it was).  INTEGRATION.md has the contract in full.
  */
 #ifndef HIPCOMP_MANAGER_HPP
 #define HIPCOMP_MANAGER_HPP

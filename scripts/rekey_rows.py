@@ -1,0 +1,56 @@
+"""rekey_rows.py OUT.json --added NAME [NAME ...]: carry the newest profiles/rNN_rows.json over to a build that only
+ADDED kernel objects (csrc/NAME.hip), without measuring again.
+
+bench.py attaches the committed rocprof rows to its result only on the build they were measured on (the ids of
+bench.kernel_source_id / bench.device_asm_id).  A new kernel file changes both ids although no measured kernel
+changed.  This script proves that from the build at hand (csrc/build/*.gfx950.s, which build() leaves there): the
+device assembly of every object but the added ones must hash to the table's device_asm_sha16 -- the measured kernels
+are the same code, instruction for instruction -- and only then writes the same rows under the new ids, saying so
+in the table's "_how".  Anything else (a changed kernel) is refused: collect again (scripts/collect_profiles.sh)."""
+import argparse
+import glob
+import hashlib
+import json
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("out")
+ap.add_argument("--added", nargs="+", required=True)
+a = ap.parse_args()
+
+tables = sorted(glob.glob(os.path.join(ROOT, "profiles", "r??_rows.json")), reverse=True)
+tables = [t for t in tables if os.path.abspath(t) != os.path.abspath(a.out)]
+old = json.load(open(tables[0]))
+files = sorted(glob.glob(os.path.join(ROOT, "hipcomp-core_amd", "csrc", "build", "*.gfx950.s")))
+names = {os.path.basename(f).split(".")[0] for f in files}
+assert set(a.added) <= names, "not built: %s" % sorted(set(a.added) - names)
+h = hashlib.sha256()
+for path in files:                       # (bench.device_asm_id over the objects the table's build had)
+    if os.path.basename(path).split(".")[0] in a.added:
+        continue
+    h.update(os.path.basename(path).encode())
+    with open(path, "rb") as f:
+        h.update(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", f.read()))
+same = h.hexdigest()[:16]
+if same != old.get("device_asm_sha16"):
+    sys.exit("%s was measured on assembly %s; the build at hand without %s has %s: a measured kernel changed, collect again"
+             % (tables[0], old.get("device_asm_sha16"), a.added, same))
+new = dict(old)
+new["_how"] = old["_how"] + (
+    "\nCarried over by scripts/rekey_rows.py from %s (sources %s, assembly %s): this build only added %s, and the "
+    "device assembly of every other kernel object is that table's, instruction for instruction (checked from "
+    "csrc/build/*.gfx950.s); nothing was measured again." % (
+        os.path.basename(tables[0]), old.get("kernel_source_sha16"), old.get("device_asm_sha16"),
+        ", ".join("csrc/%s.hip" % n for n in a.added)))
+new["kernel_source_sha16"] = bench.kernel_source_id()
+new["device_asm_sha16"] = bench.device_asm_id()
+with open(a.out, "w") as f:
+    json.dump(new, f, indent=1)
+    f.write("\n")
+print(a.out, new["kernel_source_sha16"], new["device_asm_sha16"])
