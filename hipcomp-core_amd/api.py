@@ -30,6 +30,9 @@ DEFAULT_LIB = os.path.join(_HERE, "lib", "libhipcomp.so")
 # the same sources built with -DHC_MEASUREMENT_KNOBS (csrc/Makefile VARIANT=knobs): honours
 # HIPCOMP_LZ4_SHAPE / HIPCOMP_LZ4_GEOMETRY / HIPCOMP_LZ4_SPAN -- tests and measurement scripts only
 KNOBS_LIB = os.path.join(_HERE, "lib", "libhipcomp_knobs.so")
+# the batched Deflate decoder (include/hipcomp/deflate.h, csrc/deflate/): a companion library, so that
+# libhipcomp.so stays exactly the reference's surface
+DEFLATE_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate.so")
 
 
 class hipcompStatus:
@@ -181,6 +184,48 @@ def knobs_library() -> HipcompLibrary:
     if _knobs is None:
         _knobs = HipcompLibrary(KNOBS_LIB, codecs=_available_codecs(KNOBS_LIB))
     return _knobs
+
+
+class DeflateLibrary:
+    """lib/libhipcomp_deflate.so: the three functions of include/hipcomp/deflate.h, bound like the decode
+    calls of :class:`HipcompLibrary` (same argument order)."""
+
+    def __init__(self, path: str = DEFLATE_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/deflate`). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedDeflateDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
+            ("hipcompBatchedDeflateDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p]),
+            ("hipcompBatchedDeflateGetDecompressSizeAsync", [p, p, p, c_size_t, p]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedDeflateDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedDeflateDecompressGetTempSize -> status {st}")
+        return out.value
+
+
+_deflate = None
+
+
+def deflate_library() -> DeflateLibrary:
+    """The Deflate companion library, loaded at the first call (after torch, as above) and once."""
+    global _deflate
+    if _deflate is None:
+        _deflate = DeflateLibrary(DEFLATE_LIB)
+    return _deflate
 
 
 def default_library() -> HipcompLibrary:
