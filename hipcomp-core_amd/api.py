@@ -33,6 +33,8 @@ KNOBS_LIB = os.path.join(_HERE, "lib", "libhipcomp_knobs.so")
 # the batched Deflate decoder (include/hipcomp/deflate.h, csrc/deflate/): a companion library, so that
 # libhipcomp.so stays exactly the reference's surface
 DEFLATE_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate.so")
+# the batched Deflate encoder (include/hipcomp/deflate_compress.h, csrc/deflate_compress/): a second companion
+DEFLATE_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate_compress.so")
 
 
 class hipcompStatus:
@@ -86,7 +88,13 @@ class CascadedOpts(ctypes.Structure):
     ]
 
 
+class DeflateOpts(ctypes.Structure):
+    _fields_ = [("algo", c_int)]
+
+
 LZ4_DEFAULT_OPTS = LZ4Opts(hipcompType.CHAR)
+DEFLATE_DEFAULT_OPTS = DeflateOpts(0)
+DEFLATE_COMPRESS_MAX_CHUNK_BYTES = 65536
 SNAPPY_DEFAULT_OPTS = SnappyOpts(0)
 CASCADED_DEFAULT_OPTS = CascadedOpts(4096, hipcompType.INT, 2, 1, 1)
 
@@ -226,6 +234,55 @@ def deflate_library() -> DeflateLibrary:
     if _deflate is None:
         _deflate = DeflateLibrary(DEFLATE_LIB)
     return _deflate
+
+
+class DeflateCompressLibrary:
+    """lib/libhipcomp_deflate_compress.so: the three functions of include/hipcomp/deflate_compress.h, bound
+    like the compress calls of :class:`HipcompLibrary` (same argument order)."""
+
+    def __init__(self, path: str = DEFLATE_COMPRESS_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/deflate_compress`). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedDeflateCompressGetTempSize", [c_size_t, c_size_t, DeflateOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedDeflateCompressGetMaxOutputChunkSize", [c_size_t, DeflateOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedDeflateCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, DeflateOpts, p]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def compress_temp_size(self, batch: int, max_chunk: int, opts=DEFLATE_DEFAULT_OPTS) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedDeflateCompressGetTempSize(batch, max_chunk, opts, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedDeflateCompressGetTempSize -> status {st}")
+        return out.value
+
+    def max_output_chunk_size(self, max_chunk: int, opts=DEFLATE_DEFAULT_OPTS) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedDeflateCompressGetMaxOutputChunkSize(max_chunk, opts, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedDeflateCompressGetMaxOutputChunkSize -> status {st}")
+        return out.value
+
+
+_deflate_compress = None
+
+
+def deflate_compress_library() -> DeflateCompressLibrary:
+    """The Deflate encoder's library, loaded at the first call (after torch, as above) and once."""
+    global _deflate_compress
+    if _deflate_compress is None:
+        _deflate_compress = DeflateCompressLibrary(DEFLATE_COMPRESS_LIB)
+    return _deflate_compress
 
 
 def default_library() -> HipcompLibrary:

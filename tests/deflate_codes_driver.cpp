@@ -1,0 +1,194 @@
+// CPU driver of hipcomp-core_amd/csrc/deflate_compress/deflate_codes.hpp (tests/test_deflate_codes_cpu.py): the
+// header the encoder kernel includes, compiled alone with g++.  One command per input line, one output line each:
+//
+//   alpha MAXBITS N f0 .. fN-1         -> the N code lengths of build_lengths()
+//   hist f0 .. f285 g0 .. g29          -> 286 + 30 + 19 code lengths, HLIT HDIST HCLEN, dynamic and fixed cost
+//   stream KIND T tok .. tok           -> the tokens (L<byte> or M<length>,<distance>) as ONE final block of KIND
+//                                         (0 stored, 1 fixed, 2 dynamic) written with the header's functions only:
+//                                         hex of the stream, bits written, then the three costs
+#include <cstdint>
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "deflate/deflate_tables.hpp"
+#include "deflate_compress/deflate_codes.hpp"
+
+using namespace hcamd::deflate;
+
+namespace {
+
+struct Bits
+{
+  std::vector<uint8_t> bytes;
+  uint64_t count = 0;
+  void put(uint64_t v, uint32_t n)
+  {
+    for (uint32_t i = 0; i < n; ++i, ++count) {
+      if ((count & 7u) == 0)
+        bytes.push_back(0);
+      bytes.back() = (uint8_t)(bytes.back() | (((v >> i) & 1u) << (count & 7u)));
+    }
+  }
+  void align() { count = (count + 7u) & ~(uint64_t)7; }
+};
+
+struct Codes
+{
+  uint32_t lit_freq[kFixedLitLen] = {}, dist_freq[kFixedDist] = {};
+  uint8_t lit_lens[kFixedLitLen] = {}, dist_lens[kFixedDist] = {}, cl_lens[kNumCodeLen + 1] = {};
+  uint16_t lit_codes[kFixedLitLen] = {}, dist_codes[kFixedDist] = {}, cl_codes[kNumCodeLen + 1] = {};
+  uint16_t cl_syms[kMaxLitLen + kMaxDist] = {};
+  uint32_t cl_freq[kNumCodeLen + 1] = {};
+  int hlit = 0, hdist = 0, hclen = 0, ncl = 0;
+  HuffWork w;
+
+  void build()
+  {
+    build_lengths(lit_freq, kMaxLitLen, kMaxBits, w, lit_lens);
+    build_lengths(dist_freq, kMaxDist, kMaxBits, w, dist_lens);
+    hlit = trimmed_hlit(lit_lens);
+    hdist = trimmed_hdist(dist_lens);
+    ncl = code_length_stream(lit_lens, hlit, dist_lens, hdist, cl_syms, cl_freq);
+    build_code_length_lengths(cl_freq, w, cl_lens);
+    hclen = trimmed_hclen(cl_lens);
+    assign_codes(lit_lens, kMaxLitLen, w, lit_codes);
+    assign_codes(dist_lens, kMaxDist, w, dist_codes);
+    assign_codes(cl_lens, kNumCodeLen, w, cl_codes);
+  }
+  uint32_t dynamic() const { return dynamic_cost(lit_freq, dist_freq, lit_lens, dist_lens, cl_freq, cl_lens, hclen); }
+  uint32_t fixed() const { return fixed_cost(lit_freq, dist_freq); }
+};
+
+struct Token
+{
+  uint32_t len, dist, byte;
+};
+
+void write_symbols(Bits& out, const std::vector<Token>& toks, const uint8_t* ll, const uint16_t* lc, const uint8_t* dl,
+                   const uint16_t* dc)
+{
+  for (const Token& t : toks) {
+    if (t.len == 0) {
+      out.put(lc[t.byte], ll[t.byte]);
+      continue;
+    }
+    const uint32_t ls = length_symbol(t.len), ds = dist_symbol(t.dist);
+    out.put(lc[ls], ll[ls]);
+    out.put(t.len - length_base(ls - 257u), length_extra(ls - 257u));
+    out.put(dc[ds], dl[ds]);
+    out.put(t.dist - dist_base(ds), dist_extra(ds));
+  }
+  out.put(lc[kEndOfBlock], ll[kEndOfBlock]);
+}
+
+} // namespace
+
+int main()
+{
+  std::string line;
+  while (std::getline(std::cin, line)) {
+    std::istringstream in(line);
+    std::string cmd;
+    in >> cmd;
+    if (cmd == "alpha") {
+      int maxbits = 0, n = 0;
+      in >> maxbits >> n;
+      if (n > kMaxSymbols)
+        return 2;
+      uint32_t freq[kMaxSymbols] = {};
+      uint8_t lens[kMaxSymbols] = {};
+      for (int i = 0; i < n; ++i)
+        in >> freq[i];
+      HuffWork w;
+      build_lengths(freq, n, maxbits, w, lens);
+      for (int i = 0; i < n; ++i)
+        std::printf("%d%c", (int)lens[i], i + 1 < n ? ' ' : '\n');
+      if (n == 0)
+        std::printf("\n");
+    } else if (cmd == "hist") {
+      Codes c;
+      for (int i = 0; i < kMaxLitLen; ++i)
+        in >> c.lit_freq[i];
+      for (int i = 0; i < kMaxDist; ++i)
+        in >> c.dist_freq[i];
+      c.build();
+      for (int i = 0; i < kMaxLitLen; ++i)
+        std::printf("%d ", (int)c.lit_lens[i]);
+      for (int i = 0; i < kMaxDist; ++i)
+        std::printf("%d ", (int)c.dist_lens[i]);
+      for (int i = 0; i < kNumCodeLen; ++i)
+        std::printf("%d ", (int)c.cl_lens[i]);
+      std::printf("%d %d %d %u %u\n", c.hlit, c.hdist, c.hclen, c.dynamic(), c.fixed());
+    } else if (cmd == "stream") {
+      int kind = 0;
+      size_t count = 0;
+      in >> kind >> count;
+      std::vector<Token> toks;
+      std::vector<uint8_t> plain;
+      Codes c;
+      for (size_t k = 0; k < count; ++k) {
+        std::string t;
+        in >> t;
+        Token tok = {0, 0, 0};
+        if (t[0] == 'L') {
+          tok.byte = (uint32_t)std::stoul(t.substr(1));
+          plain.push_back((uint8_t)tok.byte);
+          ++c.lit_freq[tok.byte];
+        } else {
+          const size_t comma = t.find(',');
+          tok.len = (uint32_t)std::stoul(t.substr(1, comma - 1));
+          tok.dist = (uint32_t)std::stoul(t.substr(comma + 1));
+          if (tok.dist == 0 || tok.dist > plain.size())
+            return 3;
+          for (uint32_t i = 0; i < tok.len; ++i)
+            plain.push_back(plain[plain.size() - tok.dist]);
+          ++c.lit_freq[length_symbol(tok.len)];
+          ++c.dist_freq[dist_symbol(tok.dist)];
+        }
+        toks.push_back(tok);
+      }
+      c.lit_freq[kEndOfBlock] = 1;
+      c.build();
+      Bits out;
+      if (kind == kStored) {
+        if (plain.size() > kStoredBlockMax)
+          return 4;
+        out.put(1u, 3u);
+        out.align();
+        out.put(plain.size(), 16);
+        out.put(~plain.size() & 0xFFFFu, 16);
+        for (uint8_t b : plain)
+          out.put(b, 8);
+      } else if (kind == kFixed) {
+        uint8_t ll[kFixedLitLen], dl[kFixedDist];
+        uint16_t lc[kFixedLitLen], dc[kFixedDist];
+        for (int i = 0; i < kFixedLitLen; ++i)
+          ll[i] = (uint8_t)fixed_litlen_length((uint32_t)i);
+        for (int i = 0; i < kFixedDist; ++i)
+          dl[i] = (uint8_t)kFixedDistLength;
+        assign_codes(ll, kFixedLitLen, c.w, lc);
+        assign_codes(dl, kFixedDist, c.w, dc);
+        out.put(1u | (1u << 1), 3u);
+        write_symbols(out, toks, ll, lc, dl, dc);
+      } else {
+        put_dynamic_header([&](uint32_t v, uint32_t n) { out.put(v, n); }, c.hlit, c.hdist, c.hclen, c.cl_lens);
+        for (int k = 0; k < c.ncl; ++k) {
+          const uint32_t sym = c.cl_syms[k] & 0xFFu;
+          out.put(c.cl_codes[sym], c.cl_lens[sym]);
+          out.put((uint32_t)c.cl_syms[k] >> 8, code_len_extra_bits(sym));
+        }
+        write_symbols(out, toks, c.lit_lens, c.lit_codes, c.dist_lens, c.dist_codes);
+      }
+      const uint64_t written = kind == kStored ? (uint64_t)out.bytes.size() * 8u : out.count;
+      for (uint8_t b : out.bytes)
+        std::printf("%02x", b);
+      std::printf(" %llu %u %u %u\n", (unsigned long long)written, c.dynamic(), c.fixed(), stored_cost((uint32_t)plain.size()));
+    } else {
+      return 1;
+    }
+  }
+  return 0;
+}
