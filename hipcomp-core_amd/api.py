@@ -35,6 +35,9 @@ KNOBS_LIB = os.path.join(_HERE, "lib", "libhipcomp_knobs.so")
 DEFLATE_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate.so")
 # the batched Deflate encoder (include/hipcomp/deflate_compress.h, csrc/deflate_compress/): a second companion
 DEFLATE_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate_compress.so")
+# gzip / zlib / BGZF members around the Deflate codec (include/hipcomp/gzip.h, csrc/gzip/): a third companion, which
+# links the two Deflate libraries (found next to it through its run path)
+GZIP_LIB = os.path.join(_HERE, "lib", "libhipcomp_gzip.so")
 
 
 class hipcompStatus:
@@ -91,6 +94,15 @@ class CascadedOpts(ctypes.Structure):
 class DeflateOpts(ctypes.Structure):
     _fields_ = [("algo", c_int)]
 
+
+class GzipOpts(ctypes.Structure):
+    _fields_ = [("wrapper", c_int)]
+
+
+WRAPPER_GZIP, WRAPPER_ZLIB, WRAPPER_BGZF = 0, 1, 2
+WRAPPERS = {"gzip": WRAPPER_GZIP, "zlib": WRAPPER_ZLIB, "bgzf": WRAPPER_BGZF}
+BGZF_MAX_CHUNK_BYTES = 65280
+BGZF_EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 LZ4_DEFAULT_OPTS = LZ4Opts(hipcompType.CHAR)
 DEFLATE_DEFAULT_OPTS = DeflateOpts(0)
@@ -283,6 +295,79 @@ def deflate_compress_library() -> DeflateCompressLibrary:
     if _deflate_compress is None:
         _deflate_compress = DeflateCompressLibrary(DEFLATE_COMPRESS_LIB)
     return _deflate_compress
+
+
+class GzipLibrary:
+    """lib/libhipcomp_gzip.so: the seven functions of include/hipcomp/gzip.h (same argument order)."""
+
+    def __init__(self, path: str = GZIP_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/gzip`, after the two Deflate libraries). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedGzipDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
+            ("hipcompBatchedGzipGetDecompressSizeAsync", [p, p, p, c_size_t, c_int, p, c_size_t, p]),
+            ("hipcompBatchedGzipDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, c_int, p]),
+            ("hipcompBatchedGzipCompressGetTempSize", [c_size_t, c_size_t, GzipOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedGzipCompressGetMaxOutputChunkSize", [c_size_t, GzipOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedGzipCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, GzipOpts, p]),
+            ("hipcompBgzfSplitHost", [c_void_p, c_size_t, POINTER(c_size_t), c_size_t, POINTER(c_size_t), POINTER(c_size_t)]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedGzipDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedGzipDecompressGetTempSize -> status {st}")
+        return out.value
+
+    def compress_temp_size(self, batch: int, max_chunk: int, wrapper: int = WRAPPER_GZIP) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedGzipCompressGetTempSize(batch, max_chunk, GzipOpts(wrapper), ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedGzipCompressGetTempSize -> status {st}")
+        return out.value
+
+    def max_output_chunk_size(self, max_chunk: int, wrapper: int = WRAPPER_GZIP) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedGzipCompressGetMaxOutputChunkSize(max_chunk, GzipOpts(wrapper), ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedGzipCompressGetMaxOutputChunkSize -> status {st}")
+        return out.value
+
+    def bgzf_split(self, data: bytes, capacity=None):
+        """hipcompBgzfSplitHost on a BGZF file in host memory: -> (block offsets, where the walk stopped);
+        the file was whole exactly when that is len(data).  Block i is data[offsets[i]:offsets[i + 1]], the last
+        one ends where the walk stopped."""
+        if capacity is None:
+            capacity = len(data) // 28 + 1   # no BGZF block is shorter than the empty one
+        offsets = (c_size_t * max(capacity, 1))()
+        count, stopped = c_size_t(0), c_size_t(0)
+        st = self.hipcompBgzfSplitHost(ctypes.c_char_p(data), len(data), offsets, capacity,
+                                       ctypes.byref(count), ctypes.byref(stopped))
+        if st != 0:
+            raise RuntimeError(f"hipcompBgzfSplitHost -> status {st}")
+        return list(offsets[:count.value]), stopped.value
+
+
+_gzip = None
+
+
+def gzip_library() -> GzipLibrary:
+    """The gzip companion library, loaded at the first call (after torch, as above) and once."""
+    global _gzip
+    if _gzip is None:
+        _gzip = GzipLibrary(GZIP_LIB)
+    return _gzip
 
 
 def default_library() -> HipcompLibrary:

@@ -262,3 +262,85 @@ class DeflateEncoder:
         temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
         _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedDeflateCompressAsync")
         return dst
+
+
+class GzipCodec:
+    """gzip, zlib or BGZF members around the Deflate codec (include/hipcomp/gzip.h, lib/libhipcomp_gzip.so) over
+    ChunkBatch, shaped like :class:`DeflateEncoder` and :class:`DeflateDecoder`: chunk i becomes, or is, one member
+    with its header and its verified CRC-32 / Adler-32 trailer.  Chunks to compress hold at most 65536 bytes
+    (BGZF: 65280)."""
+
+    def __init__(self, wrapper: str = "gzip", lib=None):
+        if wrapper not in api.WRAPPERS:
+            raise ValueError(f"wrapper must be one of {sorted(api.WRAPPERS)}, not {wrapper!r}")
+        self.name = wrapper
+        self.wrapper = api.WRAPPERS[wrapper]
+        self.opts = api.GzipOpts(self.wrapper)
+        self.lib = lib or api.gzip_library()
+
+    # -- size queries ----------------------------------------------------
+    def compress_temp_size(self, batch: int, max_chunk: int) -> int:
+        return self.lib.compress_temp_size(batch, max_chunk, self.wrapper)
+
+    def max_output_chunk_size(self, max_chunk: int) -> int:
+        return self.lib.max_output_chunk_size(max_chunk, self.wrapper)
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        return self.lib.decompress_temp_size(num_chunks, max_chunk)
+
+    # -- async calls (raw: caller owns every buffer) -----------------------
+    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
+                       dst: ChunkBatch, stream=None) -> int:
+        return self.lib.hipcompBatchedGzipCompressAsync(
+            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
+
+    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
+                         temp: Optional[torch.Tensor], dst: ChunkBatch,
+                         statuses: Optional[torch.Tensor], stream=None) -> int:
+        return self.lib.hipcompBatchedGzipDecompressAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(statuses), self.wrapper, _stream_handle(stream))
+
+    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, temp: Optional[torch.Tensor],
+                                  stream=None) -> int:
+        return self.lib.hipcompBatchedGzipGetDecompressSizeAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, self.wrapper,
+            _ptr(temp), 0 if temp is None else temp.numel(), _stream_handle(stream))
+
+    # -- convenience (allocates like a caller of the C API would) ----------
+    def _decode_temp(self, comp: ChunkBatch, max_chunk: int) -> torch.Tensor:
+        return torch.empty(max(self.decompress_temp_size(comp.n, max_chunk), 8), dtype=torch.uint8, device=comp.device)
+
+    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
+        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
+        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
+        real_max = int(src.sizes.max().item()) if src.n else 0
+        if max_chunk is None:
+            max_chunk = real_max
+        if max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
+            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
+        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
+        tbytes = self.compress_temp_size(src.n, max_chunk)
+        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
+        _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedGzipCompressAsync")
+        return dst
+
+    def decompress(self, comp: ChunkBatch, out_capacity: int):
+        dev = comp.device
+        dst = alloc_batch(comp.n, out_capacity, dev)
+        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
+        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
+        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
+        _check(self.decompress_async(comp, caps, actual, self._decode_temp(comp, out_capacity), dst, statuses),
+               "hipcompBatchedGzipDecompressAsync")
+        dst.sizes = actual
+        return dst, actual, statuses
+
+    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
+        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
+        _check(self.get_decompress_size_async(comp, out, self._decode_temp(comp, 0)),
+               "hipcompBatchedGzipGetDecompressSizeAsync")
+        return out
