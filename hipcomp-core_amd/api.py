@@ -38,6 +38,8 @@ DEFLATE_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate_compress.s
 # gzip / zlib / BGZF members around the Deflate codec (include/hipcomp/gzip.h, csrc/gzip/): a third companion, which
 # links the two Deflate libraries (found next to it through its run path)
 GZIP_LIB = os.path.join(_HERE, "lib", "libhipcomp_gzip.so")
+# the batched Zstandard decoder (include/hipcomp/zstd.h, csrc/zstd/): a fourth companion, on its own
+ZSTD_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd.so")
 
 
 class hipcompStatus:
@@ -398,3 +400,45 @@ def _available_codecs(path: str):
 
 # Loading at import time makes a missing build fail loudly and early.
 default_library()
+
+
+class ZstdLibrary:
+    """lib/libhipcomp_zstd.so: the three functions of include/hipcomp/zstd.h, bound like :class:`DeflateLibrary`
+    (same argument order)."""
+
+    def __init__(self, path: str = ZSTD_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/zstd`). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedZstdDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
+            ("hipcompBatchedZstdDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p]),
+            ("hipcompBatchedZstdGetDecompressSizeAsync", [p, p, p, c_size_t, p]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedZstdDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedZstdDecompressGetTempSize -> status {st}")
+        return out.value
+
+
+_zstd = None
+
+
+def zstd_library() -> ZstdLibrary:
+    """The Zstandard companion library, loaded at the first call (after torch, as above) and once."""
+    global _zstd
+    if _zstd is None:
+        _zstd = ZstdLibrary(ZSTD_LIB)
+    return _zstd

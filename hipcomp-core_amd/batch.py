@@ -344,3 +344,45 @@ class GzipCodec:
         _check(self.get_decompress_size_async(comp, out, self._decode_temp(comp, 0)),
                "hipcompBatchedGzipGetDecompressSizeAsync")
         return out
+
+
+class ZstdDecoder:
+    """The batched Zstandard decoder (include/hipcomp/zstd.h, lib/libhipcomp_zstd.so) over ChunkBatch, shaped
+    like :class:`DeflateDecoder`: chunk i is zero or more concatenated frames.  Unlike Deflate the decoder needs
+    temp space; decompress() allocates what the library asks for."""
+
+    name = "Zstd"
+
+    def __init__(self, lib=None):
+        self.lib = lib or api.zstd_library()
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        return self.lib.decompress_temp_size(num_chunks, max_chunk)
+
+    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
+                         temp: Optional[torch.Tensor], dst: ChunkBatch,
+                         statuses: Optional[torch.Tensor], stream=None) -> int:
+        return self.lib.hipcompBatchedZstdDecompressAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(statuses), _stream_handle(stream))
+
+    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, stream=None) -> int:
+        return self.lib.hipcompBatchedZstdGetDecompressSizeAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, _stream_handle(stream))
+
+    def decompress(self, comp: ChunkBatch, out_capacity: int):
+        dev = comp.device
+        dst = alloc_batch(comp.n, out_capacity, dev)
+        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
+        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
+        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
+        temp = torch.empty(max(self.decompress_temp_size(comp.n, out_capacity), 8), dtype=torch.uint8, device=dev)
+        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses), "hipcompBatchedZstdDecompressAsync")
+        dst.sizes = actual
+        return dst, actual, statuses
+
+    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
+        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
+        _check(self.get_decompress_size_async(comp, out), "hipcompBatchedZstdGetDecompressSizeAsync")
+        return out
