@@ -40,6 +40,8 @@ DEFLATE_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate_compress.s
 GZIP_LIB = os.path.join(_HERE, "lib", "libhipcomp_gzip.so")
 # the batched Zstandard decoder (include/hipcomp/zstd.h, csrc/zstd/): a fourth companion, on its own
 ZSTD_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd.so")
+# the batched Zstandard encoder (include/hipcomp/zstd_compress.h, csrc/zstd_compress/): a fifth companion, on its own
+ZSTD_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd_compress.so")
 
 
 class hipcompStatus:
@@ -101,6 +103,10 @@ class GzipOpts(ctypes.Structure):
     _fields_ = [("wrapper", c_int)]
 
 
+class ZstdOpts(ctypes.Structure):
+    _fields_ = [("level", c_int), ("checksum", c_int)]
+
+
 WRAPPER_GZIP, WRAPPER_ZLIB, WRAPPER_BGZF = 0, 1, 2
 WRAPPERS = {"gzip": WRAPPER_GZIP, "zlib": WRAPPER_ZLIB, "bgzf": WRAPPER_BGZF}
 BGZF_MAX_CHUNK_BYTES = 65280
@@ -108,6 +114,7 @@ BGZF_EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b00030000000000
 
 LZ4_DEFAULT_OPTS = LZ4Opts(hipcompType.CHAR)
 DEFLATE_DEFAULT_OPTS = DeflateOpts(0)
+ZSTD_DEFAULT_OPTS = ZstdOpts(0, 0)
 DEFLATE_COMPRESS_MAX_CHUNK_BYTES = 65536
 SNAPPY_DEFAULT_OPTS = SnappyOpts(0)
 CASCADED_DEFAULT_OPTS = CascadedOpts(4096, hipcompType.INT, 2, 1, 1)
@@ -442,3 +449,52 @@ def zstd_library() -> ZstdLibrary:
     if _zstd is None:
         _zstd = ZstdLibrary(ZSTD_LIB)
     return _zstd
+
+
+class ZstdCompressLibrary:
+    """lib/libhipcomp_zstd_compress.so: the three functions of include/hipcomp/zstd_compress.h, bound like
+    :class:`DeflateCompressLibrary` (same argument order)."""
+
+    def __init__(self, path: str = ZSTD_COMPRESS_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/zstd_compress`). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedZstdCompressGetTempSize", [c_size_t, c_size_t, ZstdOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedZstdCompressGetMaxOutputChunkSize", [c_size_t, ZstdOpts, POINTER(c_size_t)]),
+            ("hipcompBatchedZstdCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, ZstdOpts, p]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def compress_temp_size(self, batch: int, max_chunk: int, opts=ZSTD_DEFAULT_OPTS) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedZstdCompressGetTempSize(batch, max_chunk, opts, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedZstdCompressGetTempSize -> status {st}")
+        return out.value
+
+    def max_output_chunk_size(self, max_chunk: int, opts=ZSTD_DEFAULT_OPTS) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedZstdCompressGetMaxOutputChunkSize(max_chunk, opts, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedZstdCompressGetMaxOutputChunkSize -> status {st}")
+        return out.value
+
+
+_zstd_compress = None
+
+
+def zstd_compress_library() -> ZstdCompressLibrary:
+    """The Zstandard encoder's library, loaded at the first call (after torch, as above) and once."""
+    global _zstd_compress
+    if _zstd_compress is None:
+        _zstd_compress = ZstdCompressLibrary(ZSTD_COMPRESS_LIB)
+    return _zstd_compress

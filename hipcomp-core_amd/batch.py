@@ -386,3 +386,42 @@ class ZstdDecoder:
         out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
         _check(self.get_decompress_size_async(comp, out), "hipcompBatchedZstdGetDecompressSizeAsync")
         return out
+
+
+class ZstdEncoder:
+    """The batched Zstandard encoder (include/hipcomp/zstd_compress.h, lib/libhipcomp_zstd_compress.so) over
+    ChunkBatch, shaped like :class:`DeflateEncoder`: chunk i becomes one Zstandard frame, with the content
+    checksum where ``checksum`` is set.  Chunks hold at most 65536 bytes."""
+
+    name = "Zstd"
+
+    def __init__(self, checksum: bool = False, lib=None):
+        self.lib = lib or api.zstd_compress_library()
+        self.opts = api.ZstdOpts(0, 1 if checksum else 0)
+
+    def compress_temp_size(self, batch: int, max_chunk: int) -> int:
+        return self.lib.compress_temp_size(batch, max_chunk, self.opts)
+
+    def max_output_chunk_size(self, max_chunk: int) -> int:
+        return self.lib.max_output_chunk_size(max_chunk, self.opts)
+
+    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
+                       dst: ChunkBatch, stream=None) -> int:
+        return self.lib.hipcompBatchedZstdCompressAsync(
+            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
+
+    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
+        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
+        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
+        real_max = int(src.sizes.max().item()) if src.n else 0
+        if max_chunk is None:
+            max_chunk = real_max
+        if max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
+            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
+        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
+        tbytes = self.compress_temp_size(src.n, max_chunk)
+        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
+        _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedZstdCompressAsync")
+        return dst
