@@ -42,6 +42,8 @@ GZIP_LIB = os.path.join(_HERE, "lib", "libhipcomp_gzip.so")
 ZSTD_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd.so")
 # the batched Zstandard encoder (include/hipcomp/zstd_compress.h, csrc/zstd_compress/): a fifth companion, on its own
 ZSTD_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd_compress.so")
+# the batched Zstandard decoder for frames that use dictionaries (include/hipcomp/zstd_dict.h, csrc/zstd_dict/): a sixth
+ZSTD_DICT_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd_dict.so")
 
 
 class hipcompStatus:
@@ -449,6 +451,57 @@ def zstd_library() -> ZstdLibrary:
     if _zstd is None:
         _zstd = ZstdLibrary(ZSTD_LIB)
     return _zstd
+
+
+class ZstdDictLibrary:
+    """lib/libhipcomp_zstd_dict.so: the five functions of include/hipcomp/zstd_dict.h, bound like
+    :class:`ZstdLibrary` (the decode calls take one more array, the chunks' prepared dictionaries)."""
+
+    def __init__(self, path: str = ZSTD_DICT_LIB):
+        if not os.path.exists(path):
+            raise ImportError(
+                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C hipcomp-core_amd/csrc/zstd_dict`). There is no fallback path."
+            )
+        self.path = path
+        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        p = c_void_p
+        for name, argtypes in (
+            ("hipcompBatchedZstdDictGetPreparedSize", [c_size_t, POINTER(c_size_t)]),
+            ("hipcompBatchedZstdDictPrepareAsync", [p, p, c_size_t, p, p, p, p]),
+            ("hipcompBatchedZstdDictDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
+            ("hipcompBatchedZstdDictGetDecompressSizeAsync", [p, p, p, p, c_size_t, p]),
+            ("hipcompBatchedZstdDictDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p, p]),
+        ):
+            fn = getattr(self._dll, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name, fn)
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedZstdDictGetPreparedSize(dict_bytes, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedZstdDictGetPreparedSize -> status {st}")
+        return out.value
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        out = c_size_t(0)
+        st = self.hipcompBatchedZstdDictDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
+        if st != 0:
+            raise RuntimeError(f"hipcompBatchedZstdDictDecompressGetTempSize -> status {st}")
+        return out.value
+
+
+_zstd_dict = None
+
+
+def zstd_dict_library() -> ZstdDictLibrary:
+    """The Zstandard dictionary companion library, loaded at the first call (after torch, as above) and once."""
+    global _zstd_dict
+    if _zstd_dict is None:
+        _zstd_dict = ZstdDictLibrary(ZSTD_DICT_LIB)
+    return _zstd_dict
 
 
 class ZstdCompressLibrary:

@@ -388,6 +388,69 @@ class ZstdDecoder:
         return out
 
 
+class ZstdDictDecoder:
+    """The batched Zstandard decoder for frames that use dictionaries (include/hipcomp/zstd_dict.h,
+    lib/libhipcomp_zstd_dict.so) over ChunkBatch, shaped like :class:`ZstdDecoder`.  prepare() digests
+    dictionaries into blobs on the device; the decode calls take ``prepared``, an int64 tensor with the address
+    of every chunk's blob (0: no dictionary)."""
+
+    name = "ZstdDict"
+
+    def __init__(self, lib=None):
+        self.lib = lib or api.zstd_dict_library()
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        return self.lib.prepared_size(dict_bytes)
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        return self.lib.decompress_temp_size(num_chunks, max_chunk)
+
+    def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
+                      stream=None) -> int:
+        return self.lib.hipcompBatchedZstdDictPrepareAsync(
+            _ptr(dicts.ptrs), _ptr(dicts.sizes), dicts.n, _ptr(blobs.ptrs), _ptr(capacities), _ptr(statuses),
+            _stream_handle(stream))
+
+    def prepare(self, dictionaries: Sequence[bytes], device="cuda"):
+        """-> (blobs, statuses): blob i at ``blobs.ptrs[i]`` (16-byte aligned, ``blobs.sizes[i]`` bytes), status i
+        hipcompSuccess or why dictionary i has no valid blob."""
+        dicts = from_host_chunks(dictionaries, device)
+        sizes = [self.prepared_size(len(d)) for d in dictionaries]
+        blobs = alloc_batch(dicts.n, max(sizes, default=16), device)
+        blobs.sizes = torch.tensor(sizes, dtype=torch.int64, device=device)
+        statuses = torch.full((dicts.n,), -1, dtype=torch.int32, device=device)
+        _check(self.prepare_async(dicts, blobs, blobs.sizes, statuses), "hipcompBatchedZstdDictPrepareAsync")
+        return blobs, statuses
+
+    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
+                         temp: Optional[torch.Tensor], dst: ChunkBatch, statuses: Optional[torch.Tensor],
+                         prepared: torch.Tensor, stream=None) -> int:
+        return self.lib.hipcompBatchedZstdDictDecompressAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(statuses), _ptr(prepared), _stream_handle(stream))
+
+    def get_decompress_size_async(self, comp: ChunkBatch, prepared: torch.Tensor, sizes_out: torch.Tensor, stream=None) -> int:
+        return self.lib.hipcompBatchedZstdDictGetDecompressSizeAsync(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(prepared), _ptr(sizes_out), comp.n, _stream_handle(stream))
+
+    def decompress(self, comp: ChunkBatch, out_capacity: int, prepared: torch.Tensor):
+        dev = comp.device
+        dst = alloc_batch(comp.n, out_capacity, dev)
+        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
+        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
+        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
+        temp = torch.empty(max(self.decompress_temp_size(comp.n, out_capacity), 8), dtype=torch.uint8, device=dev)
+        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses, prepared), "hipcompBatchedZstdDictDecompressAsync")
+        dst.sizes = actual
+        return dst, actual, statuses
+
+    def get_decompress_size(self, comp: ChunkBatch, prepared: torch.Tensor) -> torch.Tensor:
+        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
+        _check(self.get_decompress_size_async(comp, prepared, out), "hipcompBatchedZstdDictGetDecompressSizeAsync")
+        return out
+
+
 class ZstdEncoder:
     """The batched Zstandard encoder (include/hipcomp/zstd_compress.h, lib/libhipcomp_zstd_compress.so) over
     ChunkBatch, shaped like :class:`DeflateEncoder`: chunk i becomes one Zstandard frame, with the content

@@ -59,12 +59,15 @@ struct FrameHeader
   uint64_t content_size;
   uint64_t window;
   uint64_t skip_bytes;    // skippable frame: header and content
+  uint32_t dict_id;       // data frame: its Dictionary_ID, 0 where it has none
 };
 
+// dictionaries false: a frame with a non-zero Dictionary_ID is refused here; true: the caller applies the
+// Dictionary_ID rule (zstd_dict.hpp) to dict_id
 template <class P>
-constexpr FrameHeader parse_frame_header(P p, uint64_t n)
+constexpr FrameHeader parse_frame_header(P p, uint64_t n, bool dictionaries = false)
 {
-  FrameHeader h{kNoFrame, 0, false, false, 0, 0, 0};
+  FrameHeader h{kNoFrame, 0, false, false, 0, 0, 0, 0};
   if (n < 5)   // (what libzstd asks before it looks at a magic number)
     return h;
   const uint32_t magic = (uint32_t)read_le(p, 0, 4);
@@ -97,7 +100,9 @@ constexpr FrameHeader parse_frame_header(P p, uint64_t n)
       return h;
     h.window = (1ull << log) + ((1ull << log) >> 3) * (wd & 7u);
   }
-  if (read_le(p, at, did_bytes) != 0) // no dictionaries
+  const uint64_t did = read_le(p, at, did_bytes);
+  h.dict_id = (uint32_t)did;
+  if (did != 0 && !dictionaries)
     return h;
   at += did_bytes;
   if (fcs_bytes) {
