@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import POINTER, c_int, c_size_t, c_void_p
+from typing import NamedTuple, Optional
 
 # torch bundles its own HIP runtime (torch/lib/libamdhip64.so).  It must be in
 # the process before libhipcomp.so is loaded so that the library binds to that
@@ -30,20 +31,6 @@ DEFAULT_LIB = os.path.join(_HERE, "lib", "libhipcomp.so")
 # the same sources built with -DHC_MEASUREMENT_KNOBS (csrc/Makefile VARIANT=knobs): honours
 # HIPCOMP_LZ4_SHAPE / HIPCOMP_LZ4_GEOMETRY / HIPCOMP_LZ4_SPAN -- tests and measurement scripts only
 KNOBS_LIB = os.path.join(_HERE, "lib", "libhipcomp_knobs.so")
-# the batched Deflate decoder (include/hipcomp/deflate.h, csrc/deflate/): a companion library, so that
-# libhipcomp.so stays exactly the reference's surface
-DEFLATE_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate.so")
-# the batched Deflate encoder (include/hipcomp/deflate_compress.h, csrc/deflate_compress/): a second companion
-DEFLATE_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_deflate_compress.so")
-# gzip / zlib / BGZF members around the Deflate codec (include/hipcomp/gzip.h, csrc/gzip/): a third companion, which
-# links the two Deflate libraries (found next to it through its run path)
-GZIP_LIB = os.path.join(_HERE, "lib", "libhipcomp_gzip.so")
-# the batched Zstandard decoder (include/hipcomp/zstd.h, csrc/zstd/): a fourth companion, on its own
-ZSTD_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd.so")
-# the batched Zstandard encoder (include/hipcomp/zstd_compress.h, csrc/zstd_compress/): a fifth companion, on its own
-ZSTD_COMPRESS_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd_compress.so")
-# the batched Zstandard decoder for frames that use dictionaries (include/hipcomp/zstd_dict.h, csrc/zstd_dict/): a sixth
-ZSTD_DICT_LIB = os.path.join(_HERE, "lib", "libhipcomp_zstd_dict.so")
 
 
 class hipcompStatus:
@@ -122,58 +109,81 @@ SNAPPY_DEFAULT_OPTS = SnappyOpts(0)
 CASCADED_DEFAULT_OPTS = CascadedOpts(4096, hipcompType.INT, 2, 1, 1)
 
 _OPTS = {"LZ4": LZ4Opts, "Snappy": SnappyOpts, "Cascaded": CascadedOpts}
+_P, _SIZE_OUT = c_void_p, POINTER(c_size_t)
 
 
-def _sigs(codec: str):
-    opts = _OPTS[codec]
-    p = c_void_p
+def _compress_sigs(codec: str, opts):
     return {
-        f"hipcompBatched{codec}CompressGetTempSize": [c_size_t, c_size_t, opts, POINTER(c_size_t)],
-        f"hipcompBatched{codec}CompressGetMaxOutputChunkSize": [c_size_t, opts, POINTER(c_size_t)],
-        f"hipcompBatched{codec}CompressAsync": [p, p, c_size_t, c_size_t, p, c_size_t, p, p, opts, p],
-        f"hipcompBatched{codec}DecompressGetTempSize": [c_size_t, c_size_t, POINTER(c_size_t)],
-        f"hipcompBatched{codec}DecompressAsync": [p, p, p, p, c_size_t, p, c_size_t, p, p, p],
-        f"hipcompBatched{codec}GetDecompressSizeAsync": [p, p, p, c_size_t, p],
+        f"hipcompBatched{codec}CompressGetTempSize": [c_size_t, c_size_t, opts, _SIZE_OUT],
+        f"hipcompBatched{codec}CompressGetMaxOutputChunkSize": [c_size_t, opts, _SIZE_OUT],
+        f"hipcompBatched{codec}CompressAsync": [_P, _P, c_size_t, c_size_t, _P, c_size_t, _P, _P, opts, _P],
     }
 
 
+def _decompress_sigs(codec: str):
+    return {
+        f"hipcompBatched{codec}DecompressGetTempSize": [c_size_t, c_size_t, _SIZE_OUT],
+        f"hipcompBatched{codec}DecompressAsync": [_P, _P, _P, _P, c_size_t, _P, c_size_t, _P, _P, _P],
+        f"hipcompBatched{codec}GetDecompressSizeAsync": [_P, _P, _P, c_size_t, _P],
+    }
+
+
+def _sigs(codec: str):
+    return {**_compress_sigs(codec, _OPTS[codec]), **_decompress_sigs(codec)}
+
+
 ABI_SYMBOLS = tuple(name for codec in _OPTS for name in _sigs(codec))
+
+
+def _load(path: str, how: str):
+    """The one place that loads a shared object (after torch, as above).  RTLD_LOCAL: several libraries with
+    the same symbol names can coexist."""
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is missing: {how} There is no fallback path.")
+    return ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+
+
+def _build_hint(subdir: str = "", note: str = "") -> str:
+    return ("build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            f"(or `make -C hipcomp-core_amd/csrc{subdir}`{note}).")
+
+
+def _bind(obj, dll, sigs):
+    for name, argtypes in sigs.items():
+        fn = getattr(dll, name)  # AttributeError if not exported
+        fn.argtypes = argtypes
+        fn.restype = c_int
+        setattr(obj, name, fn)
+
+
+def _size_query(lib, name: str, *args) -> int:
+    """Call ``lib.<name>(*args, &out)``, a ...Get...Size function whose last parameter is a size_t*."""
+    out = c_size_t(0)
+    st = getattr(lib, name)(*args, ctypes.byref(out))
+    if st != 0:
+        raise RuntimeError(f"{name} -> status {st}")
+    return out.value
 
 
 class HipcompLibrary:
     """A loaded shared object exporting the batched codec C ABI."""
 
     def __init__(self, path: str = DEFAULT_LIB, codecs=("LZ4", "Snappy", "Cascaded")):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc`). There is no fallback path."
-            )
+        self._dll = _load(path, _build_hint())
         self.path = path
-        # RTLD_LOCAL: several libraries with the same symbol names can coexist
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
         self.codecs = tuple(codecs)
         for codec in self.codecs:
-            for name, argtypes in _sigs(codec).items():
-                fn = getattr(self._dll, name)  # AttributeError if not exported
-                fn.argtypes = argtypes
-                fn.restype = c_int
-                setattr(self, name, fn)
+            _bind(self, self._dll, _sigs(codec))
 
     # -- size queries as plain Python -----------------------------------
     def compress_temp_size(self, codec: str, batch: int, max_chunk: int, opts) -> int:
-        out = c_size_t(0)
-        st = getattr(self, f"hipcompBatched{codec}CompressGetTempSize")(batch, max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatched{codec}CompressGetTempSize -> status {st}")
-        return out.value
+        return _size_query(self, f"hipcompBatched{codec}CompressGetTempSize", batch, max_chunk, opts)
 
     def max_output_chunk_size(self, codec: str, max_chunk: int, opts) -> int:
-        out = c_size_t(0)
-        st = getattr(self, f"hipcompBatched{codec}CompressGetMaxOutputChunkSize")(max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatched{codec}CompressGetMaxOutputChunkSize -> status {st}")
-        return out.value
+        return _size_query(self, f"hipcompBatched{codec}CompressGetMaxOutputChunkSize", max_chunk, opts)
+
+    def decompress_temp_size(self, codec: str, num_chunks: int, max_chunk: int) -> int:
+        return _size_query(self, f"hipcompBatched{codec}DecompressGetTempSize", num_chunks, max_chunk)
 
     def cascaded_select_opts(self, ptrs: int, sizes: int, batch: int, type_tag: int, temp: int, temp_bytes: int, stream: int = 0):
         """hipcompBatchedCascadedSelectOpts (include/hipcomp/cascaded_select.h, an API of this library's own):
@@ -188,25 +198,29 @@ class HipcompLibrary:
         return opts, ratio.value
 
     def cascaded_select_temp_size(self) -> int:
-        out = c_size_t(0)
         fn = self._dll.hipcompBatchedCascadedSelectOptsGetTempSize
         fn.restype = c_int
-        fn.argtypes = [POINTER(c_size_t)]
-        assert fn(ctypes.byref(out)) == 0
-        return out.value
+        fn.argtypes = [_SIZE_OUT]
+        return _size_query(self._dll, "hipcompBatchedCascadedSelectOptsGetTempSize")
 
-    def decompress_temp_size(self, codec: str, num_chunks: int, max_chunk: int) -> int:
-        out = c_size_t(0)
-        st = getattr(self, f"hipcompBatched{codec}DecompressGetTempSize")(num_chunks, max_chunk, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatched{codec}DecompressGetTempSize -> status {st}")
-        return out.value
+
+def _available_codecs(path: str):
+    # During bring-up the library may export a subset of the codecs; bind what
+    # is there and let a missing one fail at the call site (AttributeError).
+    dll = _load(path, "run __graft_entry__.build() first.")
+    return tuple(codec for codec in _OPTS if hasattr(dll, f"hipcompBatched{codec}CompressAsync"))
 
 
 _default = None
-
-
 _knobs = None
+
+
+def default_library() -> HipcompLibrary:
+    """The product library, loaded once.  Raises ImportError if not built."""
+    global _default
+    if _default is None:
+        _default = HipcompLibrary(DEFAULT_LIB, codecs=_available_codecs(DEFAULT_LIB))
+    return _default
 
 
 def knobs_library() -> HipcompLibrary:
@@ -217,143 +231,103 @@ def knobs_library() -> HipcompLibrary:
     return _knobs
 
 
-class DeflateLibrary:
-    """lib/libhipcomp_deflate.so: the three functions of include/hipcomp/deflate.h, bound like the decode
-    calls of :class:`HipcompLibrary` (same argument order)."""
-
-    def __init__(self, path: str = DEFLATE_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/deflate`). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedDeflateDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
-            ("hipcompBatchedDeflateDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p]),
-            ("hipcompBatchedDeflateGetDecompressSizeAsync", [p, p, p, c_size_t, p]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
-
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedDeflateDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedDeflateDecompressGetTempSize -> status {st}")
-        return out.value
+# Loading at import time makes a missing build fail loudly and early.  (No companion is loaded here.)
+default_library()
 
 
-_deflate = None
+# -- the companion libraries ------------------------------------------------------------------------------
+class Companion(NamedTuple):
+    """One companion of libhipcomp.so: lib/<lib>, built by csrc/<csrc_dir>/Makefile, exporting exactly ``sigs``
+    (every function returns hipcompStatus_t); ``codec`` is the name inside ``hipcompBatched<codec>...``."""
+
+    lib: str
+    csrc_dir: str
+    codec: str
+    sigs: dict
+    build_note: str = ""
+    default_opts: object = None
+
+    @property
+    def path(self) -> str:
+        return os.path.join(_HERE, "lib", self.lib)
 
 
-def deflate_library() -> DeflateLibrary:
-    """The Deflate companion library, loaded at the first call (after torch, as above) and once."""
-    global _deflate
-    if _deflate is None:
-        _deflate = DeflateLibrary(DEFLATE_LIB)
-    return _deflate
+# The decode and compress calls have the shape of the main library's (_sigs); what differs is spelled out.
+COMPANIONS = {
+    "deflate": Companion("libhipcomp_deflate.so", "deflate", "Deflate", _decompress_sigs("Deflate")),
+    "deflate_compress": Companion("libhipcomp_deflate_compress.so", "deflate_compress", "Deflate",
+                                  _compress_sigs("Deflate", DeflateOpts), default_opts=DEFLATE_DEFAULT_OPTS),
+    "gzip": Companion("libhipcomp_gzip.so", "gzip", "Gzip", {
+        **_decompress_sigs("Gzip"), **_compress_sigs("Gzip", GzipOpts),
+        # the wrapper in front of the stream; the size scan also takes temp space
+        "hipcompBatchedGzipDecompressAsync": [_P, _P, _P, _P, c_size_t, _P, c_size_t, _P, _P, c_int, _P],
+        "hipcompBatchedGzipGetDecompressSizeAsync": [_P, _P, _P, c_size_t, c_int, _P, c_size_t, _P],
+        "hipcompBgzfSplitHost": [c_void_p, c_size_t, _SIZE_OUT, c_size_t, _SIZE_OUT, _SIZE_OUT],
+    }, build_note=", after the two Deflate libraries"),
+    "zstd": Companion("libhipcomp_zstd.so", "zstd", "Zstd", _decompress_sigs("Zstd")),
+    "zstd_compress": Companion("libhipcomp_zstd_compress.so", "zstd_compress", "Zstd",
+                               _compress_sigs("Zstd", ZstdOpts), default_opts=ZSTD_DEFAULT_OPTS),
+    "zstd_dict": Companion("libhipcomp_zstd_dict.so", "zstd_dict", "ZstdDict", {
+        **_decompress_sigs("ZstdDict"),
+        # one more array, the chunks' prepared dictionaries: after the sizes, and in front of the stream
+        "hipcompBatchedZstdDictGetDecompressSizeAsync": [_P, _P, _P, _P, c_size_t, _P],
+        "hipcompBatchedZstdDictDecompressAsync": [_P, _P, _P, _P, c_size_t, _P, c_size_t, _P, _P, _P, _P],
+        "hipcompBatchedZstdDictGetPreparedSize": [c_size_t, _SIZE_OUT],
+        "hipcompBatchedZstdDictPrepareAsync": [_P, _P, c_size_t, _P, _P, _P, _P],
+    }),
+}
+DEFLATE_LIB, DEFLATE_COMPRESS_LIB, GZIP_LIB, ZSTD_LIB, ZSTD_COMPRESS_LIB, ZSTD_DICT_LIB = (
+    COMPANIONS[k].path for k in ("deflate", "deflate_compress", "gzip", "zstd", "zstd_compress", "zstd_dict"))
 
 
-class DeflateCompressLibrary:
-    """lib/libhipcomp_deflate_compress.so: the three functions of include/hipcomp/deflate_compress.h, bound
-    like the compress calls of :class:`HipcompLibrary` (same argument order)."""
+class CompanionLibrary:
+    """One loaded companion library: the functions of its COMPANIONS entry as attributes (same argument order as
+    the header), and its size queries as plain Python -- those of them that the library exports."""
 
-    def __init__(self, path: str = DEFLATE_COMPRESS_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/deflate_compress`). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedDeflateCompressGetTempSize", [c_size_t, c_size_t, DeflateOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedDeflateCompressGetMaxOutputChunkSize", [c_size_t, DeflateOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedDeflateCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, DeflateOpts, p]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
+    companion = None   # the COMPANIONS key; the subclasses below name theirs
 
-    def compress_temp_size(self, batch: int, max_chunk: int, opts=DEFLATE_DEFAULT_OPTS) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedDeflateCompressGetTempSize(batch, max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedDeflateCompressGetTempSize -> status {st}")
-        return out.value
+    def __init__(self, path: Optional[str] = None):
+        self.spec = spec = COMPANIONS[self.companion]
+        self.path = path = path or spec.path
+        self._dll = _load(path, _build_hint("/" + spec.csrc_dir, spec.build_note))
+        _bind(self, self._dll, spec.sigs)
 
-    def max_output_chunk_size(self, max_chunk: int, opts=DEFLATE_DEFAULT_OPTS) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedDeflateCompressGetMaxOutputChunkSize(max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedDeflateCompressGetMaxOutputChunkSize -> status {st}")
-        return out.value
-
-
-_deflate_compress = None
-
-
-def deflate_compress_library() -> DeflateCompressLibrary:
-    """The Deflate encoder's library, loaded at the first call (after torch, as above) and once."""
-    global _deflate_compress
-    if _deflate_compress is None:
-        _deflate_compress = DeflateCompressLibrary(DEFLATE_COMPRESS_LIB)
-    return _deflate_compress
-
-
-class GzipLibrary:
-    """lib/libhipcomp_gzip.so: the seven functions of include/hipcomp/gzip.h (same argument order)."""
-
-    def __init__(self, path: str = GZIP_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/gzip`, after the two Deflate libraries). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedGzipDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
-            ("hipcompBatchedGzipGetDecompressSizeAsync", [p, p, p, c_size_t, c_int, p, c_size_t, p]),
-            ("hipcompBatchedGzipDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, c_int, p]),
-            ("hipcompBatchedGzipCompressGetTempSize", [c_size_t, c_size_t, GzipOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedGzipCompressGetMaxOutputChunkSize", [c_size_t, GzipOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedGzipCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, GzipOpts, p]),
-            ("hipcompBgzfSplitHost", [c_void_p, c_size_t, POINTER(c_size_t), c_size_t, POINTER(c_size_t), POINTER(c_size_t)]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
+    def _opts(self, opts):
+        return self.spec.default_opts if opts is None else opts
 
     def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedGzipDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedGzipDecompressGetTempSize -> status {st}")
-        return out.value
+        return _size_query(self, f"hipcompBatched{self.spec.codec}DecompressGetTempSize", num_chunks, max_chunk)
 
-    def compress_temp_size(self, batch: int, max_chunk: int, wrapper: int = WRAPPER_GZIP) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedGzipCompressGetTempSize(batch, max_chunk, GzipOpts(wrapper), ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedGzipCompressGetTempSize -> status {st}")
-        return out.value
+    def compress_temp_size(self, batch: int, max_chunk: int, opts=None) -> int:
+        return _size_query(self, f"hipcompBatched{self.spec.codec}CompressGetTempSize", batch, max_chunk, self._opts(opts))
 
-    def max_output_chunk_size(self, max_chunk: int, wrapper: int = WRAPPER_GZIP) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedGzipCompressGetMaxOutputChunkSize(max_chunk, GzipOpts(wrapper), ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedGzipCompressGetMaxOutputChunkSize -> status {st}")
-        return out.value
+    def max_output_chunk_size(self, max_chunk: int, opts=None) -> int:
+        return _size_query(self, f"hipcompBatched{self.spec.codec}CompressGetMaxOutputChunkSize", max_chunk, self._opts(opts))
+
+
+class DeflateLibrary(CompanionLibrary):
+    companion = "deflate"
+
+
+class DeflateCompressLibrary(CompanionLibrary):
+    companion = "deflate_compress"
+
+
+class ZstdLibrary(CompanionLibrary):
+    companion = "zstd"
+
+
+class ZstdCompressLibrary(CompanionLibrary):
+    companion = "zstd_compress"
+
+
+class GzipLibrary(CompanionLibrary):
+    """Its compress size queries take the wrapper (WRAPPER_GZIP, _ZLIB or _BGZF) where the others take opts."""
+
+    companion = "gzip"
+
+    def _opts(self, wrapper):
+        return GzipOpts(WRAPPER_GZIP if wrapper is None else wrapper)
 
     def bgzf_split(self, data: bytes, capacity=None):
         """hipcompBgzfSplitHost on a BGZF file in host memory: -> (block offsets, where the walk stopped);
@@ -370,184 +344,44 @@ class GzipLibrary:
         return list(offsets[:count.value]), stopped.value
 
 
-_gzip = None
+class ZstdDictLibrary(CompanionLibrary):
+    companion = "zstd_dict"
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        return _size_query(self, "hipcompBatchedZstdDictGetPreparedSize", dict_bytes)
+
+
+COMPANION_CLASSES = {cls.companion: cls for cls in (DeflateLibrary, DeflateCompressLibrary, GzipLibrary,
+                                                     ZstdLibrary, ZstdCompressLibrary, ZstdDictLibrary)}
+_companions = {}
+
+
+def companion_library(name: str) -> CompanionLibrary:
+    """The companion library ``name`` (a COMPANIONS key), loaded at the first call (after torch, as above) and once."""
+    if name not in _companions:
+        _companions[name] = COMPANION_CLASSES[name]()
+    return _companions[name]
+
+
+def deflate_library() -> DeflateLibrary:
+    return companion_library("deflate")
+
+
+def deflate_compress_library() -> DeflateCompressLibrary:
+    return companion_library("deflate_compress")
 
 
 def gzip_library() -> GzipLibrary:
-    """The gzip companion library, loaded at the first call (after torch, as above) and once."""
-    global _gzip
-    if _gzip is None:
-        _gzip = GzipLibrary(GZIP_LIB)
-    return _gzip
-
-
-def default_library() -> HipcompLibrary:
-    """The product library, loaded once.  Raises ImportError if not built."""
-    global _default
-    if _default is None:
-        _default = HipcompLibrary(DEFAULT_LIB, codecs=_available_codecs(DEFAULT_LIB))
-    return _default
-
-
-def _available_codecs(path: str):
-    # During bring-up the library may export a subset of the codecs; bind what
-    # is there and let a missing one fail at the call site (AttributeError).
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: run __graft_entry__.build() first. There is no fallback path."
-        )
-    dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    out = []
-    for codec in _OPTS:
-        try:
-            getattr(dll, f"hipcompBatched{codec}CompressAsync")
-            out.append(codec)
-        except AttributeError:
-            pass
-    return tuple(out)
-
-
-# Loading at import time makes a missing build fail loudly and early.
-default_library()
-
-
-class ZstdLibrary:
-    """lib/libhipcomp_zstd.so: the three functions of include/hipcomp/zstd.h, bound like :class:`DeflateLibrary`
-    (same argument order)."""
-
-    def __init__(self, path: str = ZSTD_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/zstd`). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedZstdDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
-            ("hipcompBatchedZstdDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p]),
-            ("hipcompBatchedZstdGetDecompressSizeAsync", [p, p, p, c_size_t, p]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
-
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedZstdDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedZstdDecompressGetTempSize -> status {st}")
-        return out.value
-
-
-_zstd = None
+    return companion_library("gzip")
 
 
 def zstd_library() -> ZstdLibrary:
-    """The Zstandard companion library, loaded at the first call (after torch, as above) and once."""
-    global _zstd
-    if _zstd is None:
-        _zstd = ZstdLibrary(ZSTD_LIB)
-    return _zstd
-
-
-class ZstdDictLibrary:
-    """lib/libhipcomp_zstd_dict.so: the five functions of include/hipcomp/zstd_dict.h, bound like
-    :class:`ZstdLibrary` (the decode calls take one more array, the chunks' prepared dictionaries)."""
-
-    def __init__(self, path: str = ZSTD_DICT_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/zstd_dict`). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedZstdDictGetPreparedSize", [c_size_t, POINTER(c_size_t)]),
-            ("hipcompBatchedZstdDictPrepareAsync", [p, p, c_size_t, p, p, p, p]),
-            ("hipcompBatchedZstdDictDecompressGetTempSize", [c_size_t, c_size_t, POINTER(c_size_t)]),
-            ("hipcompBatchedZstdDictGetDecompressSizeAsync", [p, p, p, p, c_size_t, p]),
-            ("hipcompBatchedZstdDictDecompressAsync", [p, p, p, p, c_size_t, p, c_size_t, p, p, p, p]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
-
-    def prepared_size(self, dict_bytes: int) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedZstdDictGetPreparedSize(dict_bytes, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedZstdDictGetPreparedSize -> status {st}")
-        return out.value
-
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedZstdDictDecompressGetTempSize(num_chunks, max_chunk, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedZstdDictDecompressGetTempSize -> status {st}")
-        return out.value
-
-
-_zstd_dict = None
-
-
-def zstd_dict_library() -> ZstdDictLibrary:
-    """The Zstandard dictionary companion library, loaded at the first call (after torch, as above) and once."""
-    global _zstd_dict
-    if _zstd_dict is None:
-        _zstd_dict = ZstdDictLibrary(ZSTD_DICT_LIB)
-    return _zstd_dict
-
-
-class ZstdCompressLibrary:
-    """lib/libhipcomp_zstd_compress.so: the three functions of include/hipcomp/zstd_compress.h, bound like
-    :class:`DeflateCompressLibrary` (same argument order)."""
-
-    def __init__(self, path: str = ZSTD_COMPRESS_LIB):
-        if not os.path.exists(path):
-            raise ImportError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C hipcomp-core_amd/csrc/zstd_compress`). There is no fallback path."
-            )
-        self.path = path
-        self._dll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        p = c_void_p
-        for name, argtypes in (
-            ("hipcompBatchedZstdCompressGetTempSize", [c_size_t, c_size_t, ZstdOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedZstdCompressGetMaxOutputChunkSize", [c_size_t, ZstdOpts, POINTER(c_size_t)]),
-            ("hipcompBatchedZstdCompressAsync", [p, p, c_size_t, c_size_t, p, c_size_t, p, p, ZstdOpts, p]),
-        ):
-            fn = getattr(self._dll, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name, fn)
-
-    def compress_temp_size(self, batch: int, max_chunk: int, opts=ZSTD_DEFAULT_OPTS) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedZstdCompressGetTempSize(batch, max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedZstdCompressGetTempSize -> status {st}")
-        return out.value
-
-    def max_output_chunk_size(self, max_chunk: int, opts=ZSTD_DEFAULT_OPTS) -> int:
-        out = c_size_t(0)
-        st = self.hipcompBatchedZstdCompressGetMaxOutputChunkSize(max_chunk, opts, ctypes.byref(out))
-        if st != 0:
-            raise RuntimeError(f"hipcompBatchedZstdCompressGetMaxOutputChunkSize -> status {st}")
-        return out.value
-
-
-_zstd_compress = None
+    return companion_library("zstd")
 
 
 def zstd_compress_library() -> ZstdCompressLibrary:
-    """The Zstandard encoder's library, loaded at the first call (after torch, as above) and once."""
-    global _zstd_compress
-    if _zstd_compress is None:
-        _zstd_compress = ZstdCompressLibrary(ZSTD_COMPRESS_LIB)
-    return _zstd_compress
+    return companion_library("zstd_compress")
+
+
+def zstd_dict_library() -> ZstdDictLibrary:
+    return companion_library("zstd_dict")

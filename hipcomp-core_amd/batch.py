@@ -108,8 +108,112 @@ def _check(status: int, what: str):
         raise RuntimeError(f"{what} returned hipcompStatus_t {status}")
 
 
-class Codec:
+def _temp(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+
+
+class _Calls:
+    """What the wrapper classes below share: ``self.lib`` exports ``hipcompBatched<abi><suffix>``, where abi is
+    the class's ``_abi`` or, without one, its ``name``."""
+
+    _abi = None
+
+    def _cname(self, suffix: str) -> str:
+        return f"hipcompBatched{self._abi or self.name}{suffix}"
+
+    def _f(self, suffix: str):
+        return getattr(self.lib, self._cname(suffix))
+
+
+class _EncodeCalls(_Calls):
+    """The compress half over ``self.lib`` and ``self.opts``: the size queries, the raw call (the caller owns
+    every buffer) and compress(), which allocates like a caller of the C API would."""
+
+    _refuses_small_max_chunk = True
+
+    def compress_temp_size(self, batch: int, max_chunk: int) -> int:
+        return self.lib.compress_temp_size(batch, max_chunk, self.opts)
+
+    def max_output_chunk_size(self, max_chunk: int) -> int:
+        return self.lib.max_output_chunk_size(max_chunk, self.opts)
+
+    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
+                       dst: ChunkBatch, stream=None) -> int:
+        return self._f("CompressAsync")(
+            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
+
+    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
+        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
+        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
+        real_max = int(src.sizes.max().item()) if src.n else 0
+        if max_chunk is None:
+            max_chunk = real_max
+        if self._refuses_small_max_chunk and max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
+            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
+        dst = alloc_batch(src.n, self.max_output_chunk_size(max(real_max, max_chunk)), src.device)
+        temp = _temp(self.compress_temp_size(src.n, max_chunk), src.device)
+        _check(self.compress_async(src, max_chunk, temp, dst), self._cname("CompressAsync"))
+        return dst
+
+
+class _DecodeCalls(_Calls):
+    """The decode half over ``self.lib``: the temp size query, the raw calls and the allocating decompress() and
+    get_decompress_size().  A class whose C calls take one more argument overrides the method that passes it."""
+
+    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
+        return self.lib.decompress_temp_size(num_chunks, max_chunk)
+
+    def _decompress_call(self, comp, out_caps, actual, temp, dst, statuses, stream, *extra) -> int:
+        return self._f("DecompressAsync")(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(statuses), *extra, _stream_handle(stream))
+
+    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
+                         temp: Optional[torch.Tensor], dst: ChunkBatch,
+                         statuses: Optional[torch.Tensor], stream=None) -> int:
+        return self._decompress_call(comp, out_caps, actual, temp, dst, statuses, stream)
+
+    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, stream=None) -> int:
+        return self._f("GetDecompressSizeAsync")(
+            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, _stream_handle(stream))
+
+    def _decode_temp(self, comp: ChunkBatch, max_chunk: int) -> Optional[torch.Tensor]:
+        return _temp(self.decompress_temp_size(comp.n, max_chunk), comp.device)
+
+    def _decompress(self, comp: ChunkBatch, out_capacity: int, *extra, with_status: bool = True):
+        """``extra``: what the class's decompress_async takes after ``statuses``."""
+        dev = comp.device
+        dst = alloc_batch(comp.n, out_capacity, dev)
+        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
+        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev) if with_status else None
+        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev) if with_status else None
+        temp = self._decode_temp(comp, out_capacity)
+        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses, *extra), self._cname("DecompressAsync"))
+        if actual is not None:
+            dst.sizes = actual
+        return dst, actual, statuses
+
+    def decompress(self, comp: ChunkBatch, out_capacity: int):
+        return self._decompress(comp, out_capacity)
+
+    def _get_decompress_size(self, comp: ChunkBatch, call) -> torch.Tensor:
+        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
+        _check(call(out), self._cname("GetDecompressSizeAsync"))
+        return out
+
+    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
+        return self._get_decompress_size(comp, lambda out: self.get_decompress_size_async(comp, out))
+
+
+class Codec(_EncodeCalls, _DecodeCalls):
     """Calls of one codec ("LZ4", "Snappy" or "Cascaded") on one library."""
+
+    # compress(): ``max_chunk`` may be below the largest chunk (for LZ4 it sizes the hash table and so takes
+    # part in the result); the output buffers are sized from the larger of the two
+    _refuses_small_max_chunk = False
 
     def __init__(self, name: str, opts=None, lib: Optional[HipcompLibrary] = None):
         self.name = name
@@ -118,9 +222,8 @@ class Codec:
             opts = {"LZ4": api.LZ4_DEFAULT_OPTS, "Snappy": api.SNAPPY_DEFAULT_OPTS,
                     "Cascaded": api.CASCADED_DEFAULT_OPTS}[name]
         self.opts = opts
-        self._f = lambda suffix: getattr(self.lib, f"hipcompBatched{name}{suffix}")
 
-    # -- size queries ----------------------------------------------------
+    # (the main library's size queries take the codec's name)
     def compress_temp_size(self, batch: int, max_chunk: int) -> int:
         return self.lib.compress_temp_size(self.name, batch, max_chunk, self.opts)
 
@@ -130,102 +233,25 @@ class Codec:
     def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
         return self.lib.decompress_temp_size(self.name, num_chunks, max_chunk)
 
-    # -- async calls (raw: caller owns every buffer) -----------------------
-    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
-                       dst: ChunkBatch, stream=None) -> int:
-        return self._f("CompressAsync")(
-            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
-
-    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
-                         temp: Optional[torch.Tensor], dst: ChunkBatch,
-                         statuses: Optional[torch.Tensor], stream=None) -> int:
-        return self._f("DecompressAsync")(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(statuses), _stream_handle(stream))
-
-    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, stream=None) -> int:
-        return self._f("GetDecompressSizeAsync")(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, _stream_handle(stream))
-
-    # -- convenience (allocates like a caller of the C API would) ----------
-    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
-        """``max_chunk`` is the value handed to the C API as
-        max_uncompressed_chunk_bytes (for LZ4 it sizes the hash table and so
-        takes part in the result); output buffers are always sized from the
-        real largest chunk."""
-        real_max = int(src.sizes.max().item()) if src.n else 0
-        if max_chunk is None:
-            max_chunk = real_max
-        dst = alloc_batch(src.n, self.max_output_chunk_size(max(real_max, max_chunk)), src.device)
-        tbytes = self.compress_temp_size(src.n, max_chunk)
-        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst), f"hipcompBatched{self.name}CompressAsync")
-        return dst
-
     def decompress(self, comp: ChunkBatch, out_capacity: int, with_status: bool = True):
-        dev = comp.device
-        dst = alloc_batch(comp.n, out_capacity, dev)
-        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
-        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev) if with_status else None
-        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev) if with_status else None
-        tbytes = self.decompress_temp_size(comp.n, out_capacity)
-        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=dev)
-        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses),
-               f"hipcompBatched{self.name}DecompressAsync")
-        if actual is not None:
-            dst.sizes = actual
-        return dst, actual, statuses
-
-    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
-        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
-        _check(self.get_decompress_size_async(comp, out), f"hipcompBatched{self.name}GetDecompressSizeAsync")
-        return out
+        return self._decompress(comp, out_capacity, with_status=with_status)
 
 
-class DeflateDecoder:
+class DeflateDecoder(_DecodeCalls):
     """The batched Deflate decoder (include/hipcomp/deflate.h, lib/libhipcomp_deflate.so) over ChunkBatch:
-    the decode half of :class:`Codec`, chunk i being one raw Deflate stream."""
+    the decode half of :class:`Codec`, chunk i being one raw Deflate stream.  It needs no temp space, and
+    decompress() passes none."""
 
     name = "Deflate"
 
     def __init__(self, lib=None):
         self.lib = lib or api.deflate_library()
 
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        return self.lib.decompress_temp_size(num_chunks, max_chunk)
-
-    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
-                         temp: Optional[torch.Tensor], dst: ChunkBatch,
-                         statuses: Optional[torch.Tensor], stream=None) -> int:
-        return self.lib.hipcompBatchedDeflateDecompressAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(statuses), _stream_handle(stream))
-
-    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, stream=None) -> int:
-        return self.lib.hipcompBatchedDeflateGetDecompressSizeAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, _stream_handle(stream))
-
-    def decompress(self, comp: ChunkBatch, out_capacity: int):
-        dev = comp.device
-        dst = alloc_batch(comp.n, out_capacity, dev)
-        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
-        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
-        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
-        _check(self.decompress_async(comp, caps, actual, None, dst, statuses), "hipcompBatchedDeflateDecompressAsync")
-        dst.sizes = actual
-        return dst, actual, statuses
-
-    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
-        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
-        _check(self.get_decompress_size_async(comp, out), "hipcompBatchedDeflateGetDecompressSizeAsync")
-        return out
+    def _decode_temp(self, comp: ChunkBatch, max_chunk: int) -> None:
+        return None
 
 
-class DeflateEncoder:
+class DeflateEncoder(_EncodeCalls):
     """The batched Deflate encoder (include/hipcomp/deflate_compress.h, lib/libhipcomp_deflate_compress.so)
     over ChunkBatch: the compress half of :class:`Codec`, chunk i becoming one raw Deflate stream.  Chunks hold
     at most 65536 bytes."""
@@ -236,39 +262,14 @@ class DeflateEncoder:
         self.lib = lib or api.deflate_compress_library()
         self.opts = api.DEFLATE_DEFAULT_OPTS if opts is None else opts
 
-    def compress_temp_size(self, batch: int, max_chunk: int) -> int:
-        return self.lib.compress_temp_size(batch, max_chunk, self.opts)
 
-    def max_output_chunk_size(self, max_chunk: int) -> int:
-        return self.lib.max_output_chunk_size(max_chunk, self.opts)
-
-    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
-                       dst: ChunkBatch, stream=None) -> int:
-        return self.lib.hipcompBatchedDeflateCompressAsync(
-            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
-
-    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
-        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
-        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
-        real_max = int(src.sizes.max().item()) if src.n else 0
-        if max_chunk is None:
-            max_chunk = real_max
-        if max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
-            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
-        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
-        tbytes = self.compress_temp_size(src.n, max_chunk)
-        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedDeflateCompressAsync")
-        return dst
-
-
-class GzipCodec:
+class GzipCodec(_EncodeCalls, _DecodeCalls):
     """gzip, zlib or BGZF members around the Deflate codec (include/hipcomp/gzip.h, lib/libhipcomp_gzip.so) over
     ChunkBatch, shaped like :class:`DeflateEncoder` and :class:`DeflateDecoder`: chunk i becomes, or is, one member
     with its header and its verified CRC-32 / Adler-32 trailer.  Chunks to compress hold at most 65536 bytes
-    (BGZF: 65280)."""
+    (BGZF: 65280).  The decode calls take the wrapper, and the size scan takes temp space too."""
+
+    _abi = "Gzip"
 
     def __init__(self, wrapper: str = "gzip", lib=None):
         if wrapper not in api.WRAPPERS:
@@ -278,75 +279,30 @@ class GzipCodec:
         self.opts = api.GzipOpts(self.wrapper)
         self.lib = lib or api.gzip_library()
 
-    # -- size queries ----------------------------------------------------
+    # (the library's compress size queries take the wrapper, not the struct)
     def compress_temp_size(self, batch: int, max_chunk: int) -> int:
         return self.lib.compress_temp_size(batch, max_chunk, self.wrapper)
 
     def max_output_chunk_size(self, max_chunk: int) -> int:
         return self.lib.max_output_chunk_size(max_chunk, self.wrapper)
 
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        return self.lib.decompress_temp_size(num_chunks, max_chunk)
-
-    # -- async calls (raw: caller owns every buffer) -----------------------
-    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
-                       dst: ChunkBatch, stream=None) -> int:
-        return self.lib.hipcompBatchedGzipCompressAsync(
-            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
-
     def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
                          temp: Optional[torch.Tensor], dst: ChunkBatch,
                          statuses: Optional[torch.Tensor], stream=None) -> int:
-        return self.lib.hipcompBatchedGzipDecompressAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(statuses), self.wrapper, _stream_handle(stream))
+        return self._decompress_call(comp, out_caps, actual, temp, dst, statuses, stream, self.wrapper)
 
     def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, temp: Optional[torch.Tensor],
                                   stream=None) -> int:
-        return self.lib.hipcompBatchedGzipGetDecompressSizeAsync(
+        return self._f("GetDecompressSizeAsync")(
             _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, self.wrapper,
             _ptr(temp), 0 if temp is None else temp.numel(), _stream_handle(stream))
 
-    # -- convenience (allocates like a caller of the C API would) ----------
-    def _decode_temp(self, comp: ChunkBatch, max_chunk: int) -> torch.Tensor:
-        return torch.empty(max(self.decompress_temp_size(comp.n, max_chunk), 8), dtype=torch.uint8, device=comp.device)
-
-    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
-        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
-        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
-        real_max = int(src.sizes.max().item()) if src.n else 0
-        if max_chunk is None:
-            max_chunk = real_max
-        if max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
-            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
-        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
-        tbytes = self.compress_temp_size(src.n, max_chunk)
-        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedGzipCompressAsync")
-        return dst
-
-    def decompress(self, comp: ChunkBatch, out_capacity: int):
-        dev = comp.device
-        dst = alloc_batch(comp.n, out_capacity, dev)
-        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
-        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
-        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
-        _check(self.decompress_async(comp, caps, actual, self._decode_temp(comp, out_capacity), dst, statuses),
-               "hipcompBatchedGzipDecompressAsync")
-        dst.sizes = actual
-        return dst, actual, statuses
-
     def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
-        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
-        _check(self.get_decompress_size_async(comp, out, self._decode_temp(comp, 0)),
-               "hipcompBatchedGzipGetDecompressSizeAsync")
-        return out
+        temp = self._decode_temp(comp, 0)
+        return self._get_decompress_size(comp, lambda out: self.get_decompress_size_async(comp, out, temp))
 
 
-class ZstdDecoder:
+class ZstdDecoder(_DecodeCalls):
     """The batched Zstandard decoder (include/hipcomp/zstd.h, lib/libhipcomp_zstd.so) over ChunkBatch, shaped
     like :class:`DeflateDecoder`: chunk i is zero or more concatenated frames.  Unlike Deflate the decoder needs
     temp space; decompress() allocates what the library asks for."""
@@ -356,39 +312,8 @@ class ZstdDecoder:
     def __init__(self, lib=None):
         self.lib = lib or api.zstd_library()
 
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        return self.lib.decompress_temp_size(num_chunks, max_chunk)
 
-    def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
-                         temp: Optional[torch.Tensor], dst: ChunkBatch,
-                         statuses: Optional[torch.Tensor], stream=None) -> int:
-        return self.lib.hipcompBatchedZstdDecompressAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(statuses), _stream_handle(stream))
-
-    def get_decompress_size_async(self, comp: ChunkBatch, sizes_out: torch.Tensor, stream=None) -> int:
-        return self.lib.hipcompBatchedZstdGetDecompressSizeAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(sizes_out), comp.n, _stream_handle(stream))
-
-    def decompress(self, comp: ChunkBatch, out_capacity: int):
-        dev = comp.device
-        dst = alloc_batch(comp.n, out_capacity, dev)
-        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
-        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
-        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
-        temp = torch.empty(max(self.decompress_temp_size(comp.n, out_capacity), 8), dtype=torch.uint8, device=dev)
-        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses), "hipcompBatchedZstdDecompressAsync")
-        dst.sizes = actual
-        return dst, actual, statuses
-
-    def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
-        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
-        _check(self.get_decompress_size_async(comp, out), "hipcompBatchedZstdGetDecompressSizeAsync")
-        return out
-
-
-class ZstdDictDecoder:
+class ZstdDictDecoder(_DecodeCalls):
     """The batched Zstandard decoder for frames that use dictionaries (include/hipcomp/zstd_dict.h,
     lib/libhipcomp_zstd_dict.so) over ChunkBatch, shaped like :class:`ZstdDecoder`.  prepare() digests
     dictionaries into blobs on the device; the decode calls take ``prepared``, an int64 tensor with the address
@@ -401,9 +326,6 @@ class ZstdDictDecoder:
 
     def prepared_size(self, dict_bytes: int) -> int:
         return self.lib.prepared_size(dict_bytes)
-
-    def decompress_temp_size(self, num_chunks: int, max_chunk: int) -> int:
-        return self.lib.decompress_temp_size(num_chunks, max_chunk)
 
     def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
                       stream=None) -> int:
@@ -425,33 +347,20 @@ class ZstdDictDecoder:
     def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
                          temp: Optional[torch.Tensor], dst: ChunkBatch, statuses: Optional[torch.Tensor],
                          prepared: torch.Tensor, stream=None) -> int:
-        return self.lib.hipcompBatchedZstdDictDecompressAsync(
-            _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(out_caps), _ptr(actual), comp.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(statuses), _ptr(prepared), _stream_handle(stream))
+        return self._decompress_call(comp, out_caps, actual, temp, dst, statuses, stream, _ptr(prepared))
 
     def get_decompress_size_async(self, comp: ChunkBatch, prepared: torch.Tensor, sizes_out: torch.Tensor, stream=None) -> int:
         return self.lib.hipcompBatchedZstdDictGetDecompressSizeAsync(
             _ptr(comp.ptrs), _ptr(comp.sizes), _ptr(prepared), _ptr(sizes_out), comp.n, _stream_handle(stream))
 
     def decompress(self, comp: ChunkBatch, out_capacity: int, prepared: torch.Tensor):
-        dev = comp.device
-        dst = alloc_batch(comp.n, out_capacity, dev)
-        caps = torch.full((comp.n,), out_capacity, dtype=torch.int64, device=dev)
-        actual = torch.full((comp.n,), -1, dtype=torch.int64, device=dev)
-        statuses = torch.full((comp.n,), -1, dtype=torch.int32, device=dev)
-        temp = torch.empty(max(self.decompress_temp_size(comp.n, out_capacity), 8), dtype=torch.uint8, device=dev)
-        _check(self.decompress_async(comp, caps, actual, temp, dst, statuses, prepared), "hipcompBatchedZstdDictDecompressAsync")
-        dst.sizes = actual
-        return dst, actual, statuses
+        return self._decompress(comp, out_capacity, prepared)
 
     def get_decompress_size(self, comp: ChunkBatch, prepared: torch.Tensor) -> torch.Tensor:
-        out = torch.full((comp.n,), -1, dtype=torch.int64, device=comp.device)
-        _check(self.get_decompress_size_async(comp, prepared, out), "hipcompBatchedZstdDictGetDecompressSizeAsync")
-        return out
+        return self._get_decompress_size(comp, lambda out: self.get_decompress_size_async(comp, prepared, out))
 
 
-class ZstdEncoder:
+class ZstdEncoder(_EncodeCalls):
     """The batched Zstandard encoder (include/hipcomp/zstd_compress.h, lib/libhipcomp_zstd_compress.so) over
     ChunkBatch, shaped like :class:`DeflateEncoder`: chunk i becomes one Zstandard frame, with the content
     checksum where ``checksum`` is set.  Chunks hold at most 65536 bytes."""
@@ -461,30 +370,3 @@ class ZstdEncoder:
     def __init__(self, checksum: bool = False, lib=None):
         self.lib = lib or api.zstd_compress_library()
         self.opts = api.ZstdOpts(0, 1 if checksum else 0)
-
-    def compress_temp_size(self, batch: int, max_chunk: int) -> int:
-        return self.lib.compress_temp_size(batch, max_chunk, self.opts)
-
-    def max_output_chunk_size(self, max_chunk: int) -> int:
-        return self.lib.max_output_chunk_size(max_chunk, self.opts)
-
-    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
-                       dst: ChunkBatch, stream=None) -> int:
-        return self.lib.hipcompBatchedZstdCompressAsync(
-            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
-
-    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
-        """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
-        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
-        real_max = int(src.sizes.max().item()) if src.n else 0
-        if max_chunk is None:
-            max_chunk = real_max
-        if max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
-            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
-        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
-        tbytes = self.compress_temp_size(src.n, max_chunk)
-        temp = torch.empty(max(tbytes, 8), dtype=torch.uint8, device=src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst), "hipcompBatchedZstdCompressAsync")
-        return dst

@@ -49,12 +49,6 @@ struct WaveLds
 };
 static_assert(sizeof(WaveLds) <= 6 * 1024, "the per-wave LDS budget of DESIGN.md section 13");
 
-__device__ __forceinline__ void lds_phase()
-{
-  // the waves' LDS operations execute in order; the compiler must keep them so across lanes
-  lds_lane_exchange_fence();
-}
-
 __device__ __forceinline__ uint32_t mod_below_512(uint32_t i, uint32_t m)
 {
   // i mod m for i < 512, 1 <= m: quotient from a float reciprocal (off by at most one at these sizes), one

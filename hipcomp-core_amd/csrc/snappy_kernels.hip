@@ -49,14 +49,6 @@ __device__ __forceinline__ uint32_t snap_hash(uint32_t v)
   return (v * ((1u << 20) + 0x2a00u + 0x6au + 1u)) >> (32 - kHashBits);
 }
 
-// lowest set bit, -1 for 0 (s_ff1_i32_b64 as it is; __builtin_ctzll(0) is undefined)
-__device__ __forceinline__ int first_set_or_minus_one(uint64_t m)
-{
-  int r;
-  asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(m));
-  return r;
-}
-
 // number of lanes below mine that are set in m
 __device__ __forceinline__ uint32_t lanes_set_below(uint64_t m)
 {

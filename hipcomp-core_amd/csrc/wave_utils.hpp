@@ -33,6 +33,11 @@ __device__ __forceinline__ uint32_t load_u32_any(cgptr p)
   return *reinterpret_cast<const HC_GLOBAL u32_unaligned*>(p);
 }
 
+__device__ __forceinline__ void store_u32_any(gptr p, uint32_t v)
+{
+  *reinterpret_cast<HC_GLOBAL u32_unaligned*>(p) = v;
+}
+
 __device__ __forceinline__ u32x4 load_u128_any(cgptr p)
 {
   return *reinterpret_cast<const HC_GLOBAL u32x4_unaligned*>(p);
@@ -78,12 +83,22 @@ __device__ __forceinline__ void lds_lane_exchange_fence()
 {
   asm volatile("" ::: "memory");
 }
+// (the name the one-wave-per-chunk kernels use for it: the end of a phase of the wave's work on its LDS)
+__device__ __forceinline__ void lds_phase() { lds_lane_exchange_fence(); }
 
 // 64-bit ballot straight from the condition (HIP's __ballot goes through a
 // VGPR 0/1 value and a second compare).
 __device__ __forceinline__ uint64_t wave_ballot(bool p)
 {
   return __builtin_amdgcn_ballot_w64(p);
+}
+
+// lowest set bit, -1 for 0 (s_ff1_i32_b64 as it is; __builtin_ctzll(0) is undefined)
+__device__ __forceinline__ int first_set_or_minus_one(uint64_t m)
+{
+  int r;
+  asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(m));
+  return r;
 }
 
 // lanes [0, n), n in [0, MAXN]; the n == 64 case is only compiled in when the

@@ -74,13 +74,6 @@ struct GBytes
 
 __device__ __forceinline__ uint32_t hash_of(uint32_t v) { return (v * 0x9E3779B1u) >> (32 - kHashBits); }
 
-__device__ __forceinline__ void lds_phase() { lds_lane_exchange_fence(); }
-
-__device__ __forceinline__ void store_u32_any(gptr p, uint32_t v)
-{
-  *reinterpret_cast<HC_GLOBAL u32_unaligned*>(p) = v;
-}
-
 // the wave reads back what its lanes stored to global memory
 __device__ __forceinline__ void global_phase()
 {
