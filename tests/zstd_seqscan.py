@@ -1,6 +1,8 @@
 """Reads the sequences of a one-block Zstandard frame back as (literal length, match length, Offset_Value), with
 tests/zstd_framegen.py's tables: what the frames of the encoder's tests are asked about beyond their content (was
-a repeat code used, which one).  Plain Python; the table-description reader is the mirror of G.write_ncount."""
+a repeat code used, which one).  tokens_of resolves the Offset_Values to offsets (the encoder's own token list);
+tokens_and_bit_ranges also says where every sequence's fields lie in the sequences' bitstream.  Plain Python; the
+table-description reader is the mirror of G.write_ncount."""
 import zstd_framegen as G
 
 
@@ -45,13 +47,17 @@ def read_ncount(b: bytes, max_sym: int):
 class BackReader:
     def __init__(self, b: bytes):
         assert b and b[-1]
-        self.acc = int.from_bytes(b, "little")
+        self.b = bytes(b) + bytes(8)
         self.left = 8 * (len(b) - 1) + b[-1].bit_length() - 1
+
+    def peek(self, n: int) -> int:   # the n <= 56 bits from `left` up
+        at = self.left >> 3
+        return int.from_bytes(self.b[at:at + 8], "little") >> (self.left & 7) & ((1 << n) - 1)
 
     def read(self, n: int) -> int:
         self.left -= n
         assert self.left >= 0
-        return self.acc >> self.left & ((1 << n) - 1)
+        return self.peek(n)
 
 
 def compressed_block(frame: bytes):
@@ -65,8 +71,11 @@ def compressed_block(frame: bytes):
     return h >> 1 & 3, frame[at + 3:at + 3 + (1 if (h >> 1 & 3) == 1 else h >> 3)]
 
 
-def sequences_of(frame: bytes):
-    """-> [(ll, ml, Offset_Value)] of the frame's compressed block, None where its block is not compressed"""
+def sequences_of(frame: bytes, ranges=None):
+    """-> [(ll, ml, Offset_Value)] of the frame's compressed block, None where its block is not compressed.
+    ranges: a list that receives (low, high, na, first) per sequence -- its fields are the bits [low, high) of the
+    bitstream (bit 0: the lowest bit of its first byte), na the bits of its state updates and its LL extra bits,
+    first their value: the bits [low, low + na)."""
     kind, b = compressed_block(frame)
     if kind != 2:
         return None
@@ -107,13 +116,50 @@ def sequences_of(frame: bytes):
     out = []
     for k in range(n):
         lc, oc, mc = tll[sll][0], tof[sof][0], tml[sml][0]
+        high = r.left
         ov = (1 << oc) + r.read(oc)
         ml = G.ML_BASE[mc] + r.read(G.ML_BITS[mc])
+        mid = r.left
         ll = G.LL_BASE[lc] + r.read(G.LL_BITS[lc])
         out.append((ll, ml, ov))
         if k + 1 < n:
             sll = tll[sll][2] + r.read(tll[sll][1])
             sml = tml[sml][2] + r.read(tml[sml][1])
             sof = tof[sof][2] + r.read(tof[sof][1])
+        if ranges is not None:
+            ranges.append((r.left, high, mid - r.left, r.peek(mid - r.left)))
     assert r.left == 0
     return out
+
+
+def resolve(seqs):
+    """[(ll, ml, Offset_Value)] -> [(ll, ml, offset)] as this encoder codes offsets: value 1 is the offset of the
+    sequence before, a value above 3 is the offset plus 3; it never writes 2 or 3 (nor 1 without literals or first)"""
+    out, prev = [], 0
+    for ll, ml, ov in seqs:
+        if ov == 1:
+            if ll == 0 or prev == 0:
+                raise ValueError("Offset_Value 1 without literals or in the first sequence")
+            off = prev
+        elif ov > 3:
+            off = ov - 3
+        else:
+            raise ValueError(f"Offset_Value {ov}: this encoder never writes it")
+        out.append((ll, ml, off))
+        prev = off
+    return out
+
+
+def tokens_of(frame: bytes):
+    """-> [(ll, ml, offset)] of the frame's compressed block, None for a raw or RLE block"""
+    seqs = sequences_of(frame)
+    return None if seqs is None else resolve(seqs)
+
+
+def tokens_and_bit_ranges(frame: bytes):
+    """-> ([(ll, ml, offset)], [(low, high, na, first)]) or None.  In the reader's order a sequence is OF extra, ML extra,
+    LL extra, then the LL, ML and OF state updates: the reverse of what one lane of the kernel appends, so `low`
+    modulo 32 is the lane's alignment in the kernel's stage and na the length of its first field."""
+    ranges = []
+    seqs = sequences_of(frame, ranges)
+    return None if seqs is None else (resolve(seqs), ranges)
