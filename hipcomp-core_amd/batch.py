@@ -370,3 +370,55 @@ class ZstdEncoder(_EncodeCalls):
     def __init__(self, checksum: bool = False, lib=None):
         self.lib = lib or api.zstd_compress_library()
         self.opts = api.ZstdOpts(0, 1 if checksum else 0)
+
+
+class ZstdDictEncoder(_EncodeCalls):
+    """The batched Zstandard encoder for frames that use dictionaries (include/hipcomp/zstd_dict_compress.h,
+    lib/libhipcomp_zstd_dict_compress.so) over ChunkBatch, shaped like :class:`ZstdEncoder`.  prepare() digests
+    dictionaries into compression blobs on the device (they are not :class:`ZstdDictDecoder`'s blobs); the compress
+    calls take ``prepared``, an int64 tensor with the address of every chunk's blob (0: no dictionary, the frame
+    of :class:`ZstdEncoder`).  Chunks hold at most 32768 bytes."""
+
+    name = "ZstdDict"
+
+    def __init__(self, checksum: bool = False, lib=None):
+        self.lib = lib or api.zstd_dict_compress_library()
+        self.opts = api.ZstdOpts(0, 1 if checksum else 0)
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        return self.lib.prepared_size(dict_bytes)
+
+    def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
+                      stream=None) -> int:
+        return self.lib.hipcompBatchedZstdDictCompressPrepareAsync(
+            _ptr(dicts.ptrs), _ptr(dicts.sizes), dicts.n, _ptr(blobs.ptrs), _ptr(capacities), _ptr(statuses),
+            _stream_handle(stream))
+
+    def prepare(self, dictionaries: Sequence[bytes], device="cuda"):
+        """-> (blobs, statuses): blob i at ``blobs.ptrs[i]`` (16-byte aligned, ``blobs.sizes[i]`` bytes), status i
+        hipcompSuccess or why dictionary i has no valid blob."""
+        dicts = from_host_chunks(dictionaries, device)
+        sizes = [self.prepared_size(len(d)) for d in dictionaries]
+        blobs = alloc_batch(dicts.n, max(sizes, default=16), device)
+        blobs.sizes = torch.tensor(sizes, dtype=torch.int64, device=device)
+        statuses = torch.full((dicts.n,), -1, dtype=torch.int32, device=device)
+        _check(self.prepare_async(dicts, blobs, blobs.sizes, statuses), "hipcompBatchedZstdDictCompressPrepareAsync")
+        return blobs, statuses
+
+    def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor], dst: ChunkBatch,
+                       prepared: torch.Tensor, stream=None) -> int:
+        return self._f("CompressAsync")(
+            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
+            _ptr(temp), 0 if temp is None else temp.numel(),
+            _ptr(dst.ptrs), _ptr(dst.sizes), _ptr(prepared), self.opts, _stream_handle(stream))
+
+    def compress(self, src: ChunkBatch, prepared: torch.Tensor, max_chunk: Optional[int] = None) -> ChunkBatch:
+        real_max = int(src.sizes.max().item()) if src.n else 0
+        if max_chunk is None:
+            max_chunk = real_max
+        if max_chunk < real_max:
+            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
+        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
+        temp = _temp(self.compress_temp_size(src.n, max_chunk), src.device)
+        _check(self.compress_async(src, max_chunk, temp, dst, prepared), self._cname("CompressAsync"))
+        return dst

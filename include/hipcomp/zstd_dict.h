@@ -5,8 +5,8 @@
  * chunks (blocks of an LSM store, messages, key-value records) with one dictionary per file or per table.
  * The five entry points live in lib/libhipcomp_zstd_dict.so.  Everything hipcomp/zstd.h says about the chunk
  * format, success, failure, the temp space, the checksum, skippable frames, its three Documented differences
- * and Containment holds here unchanged; this header says what a dictionary adds.  There is no encoder with
- * dictionaries.
+ * and Containment holds here unchanged; this header says what a dictionary adds.  The encoder with
+ * dictionaries is hipcomp/zstd_dict_compress.h, in a library of its own with a blob of its own.
  *
  * A dictionary is a buffer of at most 2^30 bytes, RAW CONTENT or FORMATTED (RFC 8878 section 5):
  *   - Raw content: any buffer shorter than 8 bytes or one that does not start with the magic number 0xEC30A437.
