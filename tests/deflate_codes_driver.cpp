@@ -6,8 +6,16 @@
 //   stream KIND T tok .. tok           -> the tokens (L<byte> or M<length>,<distance>) as ONE final block of KIND
 //                                         (0 stored, 1 fixed, 2 dynamic) written with the header's functions only:
 //                                         hex of the stream, bits written, then the three costs
+//   encode T tok .. tok                   -> the same tokens in the block kind that choose_block() picks from the header's
+//   encode @FILE                             three costs, stored output beyond 65535 bytes split as stored_blocks() says:
+//                                            hex of the stream, the kind, bits written, then the three costs.  FILE holds
+//                                            little-endian dwords n and T, the chunk's n bytes, and T triples of dwords
+//                                            (literal run, match length, distance): the kernel's records.  The literals
+//                                            are the chunk's, and those behind the last match follow without a triple.
 #include <cstdint>
 #include <cstdio>
+#include <fstream>
+#include <iterator>
 #include <iostream>
 #include <sstream>
 #include <string>
@@ -84,6 +92,119 @@ void write_symbols(Bits& out, const std::vector<Token>& toks, const uint8_t* ll,
   out.put(lc[kEndOfBlock], ll[kEndOfBlock]);
 }
 
+void write_stored(Bits& out, const std::vector<uint8_t>& plain)
+{
+  const uint32_t blocks = stored_blocks((uint32_t)plain.size());
+  size_t from = 0;
+  for (uint32_t b = 0; b < blocks; ++b) {
+    const size_t left = plain.size() - from;
+    const uint32_t n = (uint32_t)(left < kStoredBlockMax ? left : kStoredBlockMax);
+    out.put(b + 1u == blocks ? 1u : 0u, 3u);
+    out.align();
+    out.put(n, 16);
+    out.put(~n & 0xFFFFu, 16);
+    for (uint32_t i = 0; i < n; ++i)
+      out.put(plain[from + i], 8);
+    from += n;
+  }
+}
+
+void write_fixed(Bits& out, const std::vector<Token>& toks, Codes& c)
+{
+  uint8_t ll[kFixedLitLen], dl[kFixedDist];
+  uint16_t lc[kFixedLitLen], dc[kFixedDist];
+  for (int i = 0; i < kFixedLitLen; ++i)
+    ll[i] = (uint8_t)fixed_litlen_length((uint32_t)i);
+  for (int i = 0; i < kFixedDist; ++i)
+    dl[i] = (uint8_t)kFixedDistLength;
+  assign_codes(ll, kFixedLitLen, c.w, lc);
+  assign_codes(dl, kFixedDist, c.w, dc);
+  out.put(1u | (1u << 1), 3u);
+  write_symbols(out, toks, ll, lc, dl, dc);
+}
+
+void write_dynamic(Bits& out, const std::vector<Token>& toks, Codes& c)
+{
+  put_dynamic_header([&](uint32_t v, uint32_t n) { out.put(v, n); }, c.hlit, c.hdist, c.hclen, c.cl_lens);
+  for (int k = 0; k < c.ncl; ++k) {
+    const uint32_t sym = c.cl_syms[k] & 0xFFu;
+    out.put(c.cl_codes[sym], c.cl_lens[sym]);
+    out.put((uint32_t)c.cl_syms[k] >> 8, code_len_extra_bits(sym));
+  }
+  write_symbols(out, toks, c.lit_lens, c.lit_codes, c.dist_lens, c.dist_codes);
+}
+
+// one token of a command line: L<byte> or M<length>,<distance>; false where it is no token of `plain`
+bool take_token(const std::string& t, std::vector<Token>& toks, std::vector<uint8_t>& plain, Codes& c)
+{
+  Token tok = {0, 0, 0};
+  if (t.size() < 2)
+    return false;
+  if (t[0] == 'L') {
+    tok.byte = (uint32_t)std::stoul(t.substr(1));
+    if (tok.byte > 255u)
+      return false;
+    plain.push_back((uint8_t)tok.byte);
+    ++c.lit_freq[tok.byte];
+  } else {
+    const size_t comma = t.find(',');
+    if (t[0] != 'M' || comma == std::string::npos)
+      return false;
+    tok.len = (uint32_t)std::stoul(t.substr(1, comma - 1));
+    tok.dist = (uint32_t)std::stoul(t.substr(comma + 1));
+    if (tok.len < 3u || tok.len > kMaxMatch || tok.dist == 0 || tok.dist > kMaxDistance || tok.dist > plain.size())
+      return false;
+    for (uint32_t i = 0; i < tok.len; ++i)
+      plain.push_back(plain[plain.size() - tok.dist]);
+    ++c.lit_freq[length_symbol(tok.len)];
+    ++c.dist_freq[dist_symbol(tok.dist)];
+  }
+  toks.push_back(tok);
+  return true;
+}
+
+uint32_t dword_at(const std::vector<uint8_t>& b, size_t at)
+{
+  return (uint32_t)b[at] | (uint32_t)b[at + 1] << 8 | (uint32_t)b[at + 2] << 16 | (uint32_t)b[at + 3] << 24;
+}
+
+// the file of `encode @FILE` -> tokens; false where the triples are not the chunk's
+bool take_file(const std::string& path, std::vector<Token>& toks, std::vector<uint8_t>& plain, Codes& c)
+{
+  std::ifstream f(path, std::ios::binary);
+  const std::vector<uint8_t> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  if (!f || b.size() < 8)
+    return false;
+  const size_t n = dword_at(b, 0), count = dword_at(b, 4);
+  if (n > 65536 || count > n / 3 + 1 || b.size() != 8 + n + 12 * count)
+    return false;
+  const uint8_t* chunk = b.data() + 8;
+  size_t pos = 0;
+  auto literals = [&](size_t k) {
+    for (; k > 0; --k, ++pos) {
+      toks.push_back(Token{0, 0, chunk[pos]});
+      ++c.lit_freq[chunk[pos]];
+    }
+  };
+  for (size_t k = 0; k < count; ++k) {
+    const size_t at = 8 + n + 12 * k;
+    const uint32_t run = dword_at(b, at), len = dword_at(b, at + 4), dist = dword_at(b, at + 8);
+    if (run > n - pos || len < 3u || len > kMaxMatch || len > n - pos - run || dist == 0 || dist > kMaxDistance || dist > pos + run)
+      return false;
+    literals(run);
+    for (uint32_t i = 0; i < len; ++i)
+      if (chunk[pos + i] != chunk[pos + i - dist])
+        return false;
+    toks.push_back(Token{len, dist, 0});
+    ++c.lit_freq[length_symbol(len)];
+    ++c.dist_freq[dist_symbol(dist)];
+    pos += len;
+  }
+  literals(n - pos);
+  plain.assign(chunk, chunk + n);
+  return true;
+}
+
 } // namespace
 
 int main()
@@ -132,23 +253,8 @@ int main()
       for (size_t k = 0; k < count; ++k) {
         std::string t;
         in >> t;
-        Token tok = {0, 0, 0};
-        if (t[0] == 'L') {
-          tok.byte = (uint32_t)std::stoul(t.substr(1));
-          plain.push_back((uint8_t)tok.byte);
-          ++c.lit_freq[tok.byte];
-        } else {
-          const size_t comma = t.find(',');
-          tok.len = (uint32_t)std::stoul(t.substr(1, comma - 1));
-          tok.dist = (uint32_t)std::stoul(t.substr(comma + 1));
-          if (tok.dist == 0 || tok.dist > plain.size())
-            return 3;
-          for (uint32_t i = 0; i < tok.len; ++i)
-            plain.push_back(plain[plain.size() - tok.dist]);
-          ++c.lit_freq[length_symbol(tok.len)];
-          ++c.dist_freq[dist_symbol(tok.dist)];
-        }
-        toks.push_back(tok);
+        if (!take_token(t, toks, plain, c))
+          return 3;
       }
       c.lit_freq[kEndOfBlock] = 1;
       c.build();
@@ -156,36 +262,51 @@ int main()
       if (kind == kStored) {
         if (plain.size() > kStoredBlockMax)
           return 4;
-        out.put(1u, 3u);
-        out.align();
-        out.put(plain.size(), 16);
-        out.put(~plain.size() & 0xFFFFu, 16);
-        for (uint8_t b : plain)
-          out.put(b, 8);
+        write_stored(out, plain);
       } else if (kind == kFixed) {
-        uint8_t ll[kFixedLitLen], dl[kFixedDist];
-        uint16_t lc[kFixedLitLen], dc[kFixedDist];
-        for (int i = 0; i < kFixedLitLen; ++i)
-          ll[i] = (uint8_t)fixed_litlen_length((uint32_t)i);
-        for (int i = 0; i < kFixedDist; ++i)
-          dl[i] = (uint8_t)kFixedDistLength;
-        assign_codes(ll, kFixedLitLen, c.w, lc);
-        assign_codes(dl, kFixedDist, c.w, dc);
-        out.put(1u | (1u << 1), 3u);
-        write_symbols(out, toks, ll, lc, dl, dc);
+        write_fixed(out, toks, c);
       } else {
-        put_dynamic_header([&](uint32_t v, uint32_t n) { out.put(v, n); }, c.hlit, c.hdist, c.hclen, c.cl_lens);
-        for (int k = 0; k < c.ncl; ++k) {
-          const uint32_t sym = c.cl_syms[k] & 0xFFu;
-          out.put(c.cl_codes[sym], c.cl_lens[sym]);
-          out.put((uint32_t)c.cl_syms[k] >> 8, code_len_extra_bits(sym));
-        }
-        write_symbols(out, toks, c.lit_lens, c.lit_codes, c.dist_lens, c.dist_codes);
+        write_dynamic(out, toks, c);
       }
       const uint64_t written = kind == kStored ? (uint64_t)out.bytes.size() * 8u : out.count;
       for (uint8_t b : out.bytes)
         std::printf("%02x", b);
       std::printf(" %llu %u %u %u\n", (unsigned long long)written, c.dynamic(), c.fixed(), stored_cost((uint32_t)plain.size()));
+    } else if (cmd == "encode") {
+      std::string first;
+      in >> first;
+      std::vector<Token> toks;
+      std::vector<uint8_t> plain;
+      Codes c;
+      if (!first.empty() && first[0] == '@') {
+        if (!take_file(first.substr(1), toks, plain, c))
+          return 5;
+      } else {
+        const size_t count = (size_t)std::stoul(first);
+        for (size_t k = 0; k < count; ++k) {
+          std::string t;
+          in >> t;
+          if (!take_token(t, toks, plain, c))
+            return 3;
+        }
+        if (plain.size() > 65536)
+          return 4;
+      }
+      c.lit_freq[kEndOfBlock] = 1;
+      c.build();
+      const uint32_t dyn = c.dynamic(), fix = c.fixed(), stored = stored_cost((uint32_t)plain.size());
+      const BlockKind kind = choose_block(stored, fix, dyn);
+      Bits out;
+      if (kind == kStored)
+        write_stored(out, plain);
+      else if (kind == kFixed)
+        write_fixed(out, toks, c);
+      else
+        write_dynamic(out, toks, c);
+      const uint64_t written = kind == kStored ? (uint64_t)out.bytes.size() * 8u : out.count;
+      for (uint8_t b : out.bytes)
+        std::printf("%02x", b);
+      std::printf(" %d %llu %u %u %u\n", (int)kind, (unsigned long long)written, dyn, fix, stored);
     } else {
       return 1;
     }

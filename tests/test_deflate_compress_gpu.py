@@ -81,17 +81,21 @@ def inflate(stream: bytes):
 
 
 def compress_guarded(hc, torch, dev, chunks, max_chunk=MAX_CHUNK, offsets=(0,), turn=0):
-    """-> (streams, sizes): every chunk compressed inside guarded slots; containment is asserted here"""
+    """-> (streams, sizes): every chunk compressed inside guarded slots, the temp space -- exactly the size the
+    library asks for -- in one too; containment is asserted here"""
     n = len(chunks)
     cap = bound(max_chunk)
     src = GuardedSlots(torch, [len(c) for c in chunks], dev, offsets=offsets, turn=turn, seed=21, chunks=chunks)
     dst = GuardedSlots(torch, [cap] * n, dev, offsets=offsets, turn=turn + 3, seed=22)
     enc = hc.batch.DeflateEncoder()
-    temp = torch.empty(max(enc.compress_temp_size(n, max_chunk), 8), dtype=torch.uint8, device=dev)
+    temp_size = enc.compress_temp_size(n, max_chunk)
+    temp = GuardedSlots(torch, [temp_size], dev, seed=23)
+    at = int(temp.at[0])
     out_batch = dst.batch(hc)
     out_batch.sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
-    assert enc.compress_async(src.batch(hc), max_chunk, temp, out_batch) == 0
+    assert enc.compress_async(src.batch(hc), max_chunk, temp.data[at:at + temp_size], out_batch) == 0
     torch.cuda.synchronize()
+    assert temp.first_guard_change() is None, temp.first_guard_change()      # every wave stays in its token buffer
     assert src.unchanged() is None, src.unchanged()                      # the input is only read
     got = dst.after()
     assert dst.first_guard_change(got) is None, dst.first_guard_change(got)   # nothing at or beyond out_i + bound

@@ -90,9 +90,11 @@ def _words(data: bytes):
     return w.tolist(), h.tolist()
 
 
-def _match_length(data: bytes, mp: int, dist: int) -> int:
-    """bytes from mp on that equal those dist before them, to the chunk's end"""
+def _match_length(data: bytes, mp: int, dist: int, max_match=None) -> int:
+    """bytes from mp on that equal those dist before them, to the chunk's end or to max_match"""
     n, done, step = len(data), 4, 64
+    if max_match is not None:
+        n = min(n, mp + max_match)
     while mp + done < n:
         k = min(step, n - mp - done)
         a, b = data[mp + done:mp + done + k], data[mp + done - dist:mp + done - dist + k]
@@ -104,11 +106,14 @@ def _match_length(data: bytes, mp: int, dist: int) -> int:
     return done
 
 
-def parse(data: bytes, copies=None):
+def parse(data: bytes, copies=None, max_match=None, max_distance=None):
     """The encoder's parse of `data`: -> [(ll, ml, offset)], None where no parse runs (fewer than 4 bytes, or all
-    bytes equal).  copies: {position: planned source}, checked as the module's docstring says."""
+    bytes equal: Zstandard's RLE_Block).  copies: {position: planned source}, checked as the module's docstring says.
+    max_match, max_distance: the Deflate encoder's form of the rule (tests/deflate_inputgen.py) -- a candidate
+    further back than max_distance is no hit, a match stops at max_match and the next trip starts at its end, so the
+    same distance can follow with no literal between; all bytes equal are parsed like any others."""
     n = len(data)
-    if n <= 3 or data == data[:1] * n:
+    if n <= 3 or (max_match is None and data == data[:1] * n):
         return None
     copies = copies or {}
     w, h = _words(data)
@@ -127,12 +132,12 @@ def parse(data: bytes, copies=None):
                 if want is not None:
                     raise PlanError(f"the source {want} of the copy at {my} " + (
                         "shared its slot with another posting lane of its trip" if want in c else "was overwritten"))
-                if any(p < my and w[p] == w[my] for p in c):
+                if any(p < my and w[p] == w[my] and (max_distance is None or my - p <= max_distance) for p in c):
                     raise PlanError(f"the word at {my} has two candidates that the hardware chooses between")
                 continue
             if want is not None and c != want:
                 raise PlanError(f"the source {want} of the copy at {my} " + ("was overwritten" if want in ever else "was never posted"))
-            if c < my and w[c] == w[my]:
+            if c < my and w[c] == w[my] and (max_distance is None or my - c <= max_distance):
                 hit, cand = j, c
                 break
         t = in_window if hit < 0 else hit
@@ -148,7 +153,7 @@ def parse(data: bytes, copies=None):
         if hit >= 0:
             mp = pos + t
             dist = pos + hit - cand
-            ml = _match_length(data, mp, dist) if mp + 4 <= n else 4
+            ml = _match_length(data, mp, dist, max_match) if mp + 4 <= n else 4
             tokens.append((pend + t, ml, dist))
             pend, pos = 0, mp + ml
         else:
@@ -198,9 +203,10 @@ def literals_of(content: bytes, tokens) -> bytes:
 # ------------------------------------------------------------------------------------------------------ the builder
 
 class Chunk:
-    def __init__(self, seed, alphabet=LOW):
+    def __init__(self, seed, alphabet=LOW, max_match=None, max_distance=None):
         self.rng = np.random.default_rng(seed)
         self.alpha = alphabet
+        self.max_match, self.max_distance = max_match, max_distance
         self.buf = bytearray()
         self.words = set()         # every 4-byte word of the chunk so far
         self.used = set()          # their slots
@@ -282,9 +288,12 @@ class Chunk:
         return pos
 
     def copy(self, L, src):
-        """a copy of L >= 4 bytes from position src (it may run into itself): the token (literals so far, L, offset)"""
+        """a copy of L >= 4 bytes from position src (it may run into itself): the token (literals so far, L, offset).
+        With max_match a longer copy is as many tokens as it takes, the later ones behind no literal; fewer than 4
+        bytes left over are literals of the next run."""
         q = len(self.buf)
         assert L >= 4 and 0 <= src < q and q + L <= MAX_CHUNK
+        assert self.max_distance is None or q - src <= self.max_distance
         if self.forbid is not None and self.buf[src] == self.forbid:
             raise PlanError("the copy's first byte is the one that has to differ")
         for i in range(L):
@@ -294,9 +303,15 @@ class Chunk:
             if w in self.words or zhash(w) in self.reserved:
                 raise PlanError("a literal word that the copy completes occurs earlier or takes a source's slot")
         self._see(q - 3)
-        self.tokens.append((self.run, L, q - src))
-        self.copies[q] = src
-        self.run = 0
+        step = L if self.max_match is None else self.max_match
+        for done in range(0, L, step):
+            piece = min(step, L - done)
+            if piece < 4:
+                self.run = piece
+                break
+            self.tokens.append((self.run, piece, q - src))
+            self.copies[q + done] = src + done
+            self.run = 0
         self.forbid = self.buf[src + L]
         self.trip0 = q + L
         return q
@@ -338,13 +353,13 @@ class Chunk:
         return Case(name, self.buf, list(self.tokens), self.copies, tags)
 
 
-def _build(seed, fn, alphabet=LOW, tries=60):
+def _build(seed, fn, alphabet=LOW, tries=60, max_match=None, max_distance=None):
     """fn(Chunk) -> Case whose plan parse() confirms, with the next salt of the seed whenever it does not"""
     err = None
     for salt in range(tries):
         try:
-            case = fn(Chunk(list(seed) + [salt], alphabet))
-            got = parse(case.content, case.copies)
+            case = fn(Chunk(list(seed) + [salt], alphabet, max_match, max_distance))
+            got = parse(case.content, case.copies, max_match, max_distance)
             if got != case.tokens and not (got is None and not case.tokens):
                 raise PlanError(f"{case.name}: the parse differs from the plan")
             return case
