@@ -275,14 +275,6 @@ COMPANIONS = {
         "hipcompBatchedZstdDictGetPreparedSize": [c_size_t, _SIZE_OUT],
         "hipcompBatchedZstdDictPrepareAsync": [_P, _P, c_size_t, _P, _P, _P, _P],
     }),
-}
-DEFLATE_LIB, DEFLATE_COMPRESS_LIB, GZIP_LIB, ZSTD_LIB, ZSTD_COMPRESS_LIB, ZSTD_DICT_LIB = (
-    COMPANIONS[k].path for k in ("deflate", "deflate_compress", "gzip", "zstd", "zstd_compress", "zstd_dict"))
-
-
-# Companions added after the six above.  They are built, bound and guarded in the same way; the table is a second
-# one only because tests/test_companion_build_cpu.py pins the first to exactly six names.
-LATER_COMPANIONS = {
     "zstd_dict_compress": Companion("libhipcomp_zstd_dict_compress.so", "zstd_dict_compress", "ZstdDict", {
         # the compress calls of zstd_compress with one more array, the chunks' prepared dictionaries, in front of the
         # opts; the prepare calls in the shape of zstd_dict's
@@ -293,22 +285,18 @@ LATER_COMPANIONS = {
         "hipcompBatchedZstdDictCompressPrepareAsync": [_P, _P, c_size_t, _P, _P, _P, _P],
     }, default_opts=ZSTD_DEFAULT_OPTS),
 }
-ZSTD_DICT_COMPRESS_LIB = LATER_COMPANIONS["zstd_dict_compress"].path
-
-
-def companion_spec(name: str) -> Companion:
-    """The description of companion ``name``, from either table."""
-    return COMPANIONS[name] if name in COMPANIONS else LATER_COMPANIONS[name]
+(DEFLATE_LIB, DEFLATE_COMPRESS_LIB, GZIP_LIB, ZSTD_LIB, ZSTD_COMPRESS_LIB, ZSTD_DICT_LIB,
+ ZSTD_DICT_COMPRESS_LIB) = (spec.path for spec in COMPANIONS.values())   # in the table's order
 
 
 class CompanionLibrary:
-    """One loaded companion library: the functions of its COMPANIONS (or LATER_COMPANIONS) entry as attributes (same
-    argument order as the header), and its size queries as plain Python -- those of them that the library exports."""
+    """One loaded companion library: the functions of its COMPANIONS entry as attributes (same argument order as
+    the header), and its size queries as plain Python -- those of them that the library exports."""
 
     companion = None   # the COMPANIONS key; the subclasses below name theirs
 
     def __init__(self, path: Optional[str] = None):
-        self.spec = spec = companion_spec(self.companion)
+        self.spec = spec = COMPANIONS[self.companion]
         self.path = path = path or spec.path
         self._dll = _load(path, _build_hint("/" + spec.csrc_dir, spec.build_note))
         _bind(self, self._dll, spec.sigs)
@@ -379,16 +367,15 @@ class ZstdDictCompressLibrary(CompanionLibrary):
         return _size_query(self, "hipcompBatchedZstdDictCompressGetPreparedSize", dict_bytes)
 
 
-COMPANION_CLASSES = {cls.companion: cls for cls in (DeflateLibrary, DeflateCompressLibrary, GzipLibrary,
-                                                     ZstdLibrary, ZstdCompressLibrary, ZstdDictLibrary)}
-LATER_COMPANION_CLASSES = {cls.companion: cls for cls in (ZstdDictCompressLibrary,)}
+COMPANION_CLASSES = {cls.companion: cls for cls in (DeflateLibrary, DeflateCompressLibrary, GzipLibrary, ZstdLibrary,
+                                                     ZstdCompressLibrary, ZstdDictLibrary, ZstdDictCompressLibrary)}
 _companions = {}
 
 
 def companion_library(name: str) -> CompanionLibrary:
     """The companion library ``name`` (a COMPANIONS key), loaded at the first call (after torch, as above) and once."""
     if name not in _companions:
-        _companions[name] = (COMPANION_CLASSES[name] if name in COMPANION_CLASSES else LATER_COMPANION_CLASSES[name])()
+        _companions[name] = COMPANION_CLASSES[name]()
     return _companions[name]
 
 

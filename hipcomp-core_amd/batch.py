@@ -118,11 +118,11 @@ class _Calls:
 
     _abi = None
 
-    def _cname(self, suffix: str) -> str:
-        return f"hipcompBatched{self._abi or self.name}{suffix}"
+    def _cname(self, suffix: str, abi: Optional[str] = None) -> str:
+        return f"hipcompBatched{abi or self._abi or self.name}{suffix}"
 
-    def _f(self, suffix: str):
-        return getattr(self.lib, self._cname(suffix))
+    def _f(self, suffix: str, abi: Optional[str] = None):
+        return getattr(self.lib, self._cname(suffix, abi))
 
 
 class _EncodeCalls(_Calls):
@@ -138,23 +138,26 @@ class _EncodeCalls(_Calls):
         return self.lib.max_output_chunk_size(max_chunk, self.opts)
 
     def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor],
-                       dst: ChunkBatch, stream=None) -> int:
+                       dst: ChunkBatch, stream=None, *extra) -> int:
+        """``extra``: what the class's C call takes in front of the opts."""
         return self._f("CompressAsync")(
             _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
             _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), self.opts, _stream_handle(stream))
+            _ptr(dst.ptrs), _ptr(dst.sizes), *extra, self.opts, _stream_handle(stream))
 
-    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None) -> ChunkBatch:
+    def compress(self, src: ChunkBatch, max_chunk: Optional[int] = None, *extra) -> ChunkBatch:
         """``max_chunk`` is the value handed to the C API as max_uncompressed_chunk_bytes (it sizes the temp
-        space and the output slots, the bytes do not depend on it); by default the real largest chunk."""
+        space and the output slots, the bytes do not depend on it); by default the real largest chunk.
+        ``extra``: what the class's compress_async takes after ``dst``."""
         real_max = int(src.sizes.max().item()) if src.n else 0
         if max_chunk is None:
             max_chunk = real_max
         if self._refuses_small_max_chunk and max_chunk < real_max:   # (the C call would leave such a chunk uncompressed, with size 0)
             raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
+        # (where a small max_chunk is refused, max_chunk >= real_max here and the larger of the two is max_chunk itself)
         dst = alloc_batch(src.n, self.max_output_chunk_size(max(real_max, max_chunk)), src.device)
         temp = _temp(self.compress_temp_size(src.n, max_chunk), src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst), self._cname("CompressAsync"))
+        _check(self.compress_async(src, max_chunk, temp, dst, *extra), self._cname("CompressAsync"))
         return dst
 
 
@@ -206,6 +209,33 @@ class _DecodeCalls(_Calls):
 
     def get_decompress_size(self, comp: ChunkBatch) -> torch.Tensor:
         return self._get_decompress_size(comp, lambda out: self.get_decompress_size_async(comp, out))
+
+
+class _PrepareCalls(_Calls):
+    """The prepare half over ``self.lib``: dictionaries become blobs on the device.  The C functions are
+    ``hipcompBatched<_prepare_abi>PrepareAsync`` and ``...GetPreparedSize``."""
+
+    _prepare_abi = None
+
+    def prepared_size(self, dict_bytes: int) -> int:
+        return api._size_query(self.lib, self._cname("GetPreparedSize", self._prepare_abi), dict_bytes)
+
+    def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
+                      stream=None) -> int:
+        return self._f("PrepareAsync", self._prepare_abi)(
+            _ptr(dicts.ptrs), _ptr(dicts.sizes), dicts.n, _ptr(blobs.ptrs), _ptr(capacities), _ptr(statuses),
+            _stream_handle(stream))
+
+    def prepare(self, dictionaries: Sequence[bytes], device="cuda"):
+        """-> (blobs, statuses): blob i at ``blobs.ptrs[i]`` (16-byte aligned, ``blobs.sizes[i]`` bytes), status i
+        hipcompSuccess or why dictionary i has no valid blob."""
+        dicts = from_host_chunks(dictionaries, device)
+        sizes = [self.prepared_size(len(d)) for d in dictionaries]
+        blobs = alloc_batch(dicts.n, max(sizes, default=16), device)
+        blobs.sizes = torch.tensor(sizes, dtype=torch.int64, device=device)
+        statuses = torch.full((dicts.n,), -1, dtype=torch.int32, device=device)
+        _check(self.prepare_async(dicts, blobs, blobs.sizes, statuses), self._cname("PrepareAsync", self._prepare_abi))
+        return blobs, statuses
 
 
 class Codec(_EncodeCalls, _DecodeCalls):
@@ -313,36 +343,16 @@ class ZstdDecoder(_DecodeCalls):
         self.lib = lib or api.zstd_library()
 
 
-class ZstdDictDecoder(_DecodeCalls):
+class ZstdDictDecoder(_DecodeCalls, _PrepareCalls):
     """The batched Zstandard decoder for frames that use dictionaries (include/hipcomp/zstd_dict.h,
     lib/libhipcomp_zstd_dict.so) over ChunkBatch, shaped like :class:`ZstdDecoder`.  prepare() digests
     dictionaries into blobs on the device; the decode calls take ``prepared``, an int64 tensor with the address
     of every chunk's blob (0: no dictionary)."""
 
-    name = "ZstdDict"
+    name = _prepare_abi = "ZstdDict"
 
     def __init__(self, lib=None):
         self.lib = lib or api.zstd_dict_library()
-
-    def prepared_size(self, dict_bytes: int) -> int:
-        return self.lib.prepared_size(dict_bytes)
-
-    def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
-                      stream=None) -> int:
-        return self.lib.hipcompBatchedZstdDictPrepareAsync(
-            _ptr(dicts.ptrs), _ptr(dicts.sizes), dicts.n, _ptr(blobs.ptrs), _ptr(capacities), _ptr(statuses),
-            _stream_handle(stream))
-
-    def prepare(self, dictionaries: Sequence[bytes], device="cuda"):
-        """-> (blobs, statuses): blob i at ``blobs.ptrs[i]`` (16-byte aligned, ``blobs.sizes[i]`` bytes), status i
-        hipcompSuccess or why dictionary i has no valid blob."""
-        dicts = from_host_chunks(dictionaries, device)
-        sizes = [self.prepared_size(len(d)) for d in dictionaries]
-        blobs = alloc_batch(dicts.n, max(sizes, default=16), device)
-        blobs.sizes = torch.tensor(sizes, dtype=torch.int64, device=device)
-        statuses = torch.full((dicts.n,), -1, dtype=torch.int32, device=device)
-        _check(self.prepare_async(dicts, blobs, blobs.sizes, statuses), "hipcompBatchedZstdDictPrepareAsync")
-        return blobs, statuses
 
     def decompress_async(self, comp: ChunkBatch, out_caps: torch.Tensor, actual: Optional[torch.Tensor],
                          temp: Optional[torch.Tensor], dst: ChunkBatch, statuses: Optional[torch.Tensor],
@@ -372,7 +382,7 @@ class ZstdEncoder(_EncodeCalls):
         self.opts = api.ZstdOpts(0, 1 if checksum else 0)
 
 
-class ZstdDictEncoder(_EncodeCalls):
+class ZstdDictEncoder(_EncodeCalls, _PrepareCalls):
     """The batched Zstandard encoder for frames that use dictionaries (include/hipcomp/zstd_dict_compress.h,
     lib/libhipcomp_zstd_dict_compress.so) over ChunkBatch, shaped like :class:`ZstdEncoder`.  prepare() digests
     dictionaries into compression blobs on the device (they are not :class:`ZstdDictDecoder`'s blobs); the compress
@@ -380,45 +390,15 @@ class ZstdDictEncoder(_EncodeCalls):
     of :class:`ZstdEncoder`).  Chunks hold at most 32768 bytes."""
 
     name = "ZstdDict"
+    _prepare_abi = "ZstdDictCompress"
 
     def __init__(self, checksum: bool = False, lib=None):
         self.lib = lib or api.zstd_dict_compress_library()
         self.opts = api.ZstdOpts(0, 1 if checksum else 0)
 
-    def prepared_size(self, dict_bytes: int) -> int:
-        return self.lib.prepared_size(dict_bytes)
-
-    def prepare_async(self, dicts: ChunkBatch, blobs: ChunkBatch, capacities: torch.Tensor, statuses: torch.Tensor,
-                      stream=None) -> int:
-        return self.lib.hipcompBatchedZstdDictCompressPrepareAsync(
-            _ptr(dicts.ptrs), _ptr(dicts.sizes), dicts.n, _ptr(blobs.ptrs), _ptr(capacities), _ptr(statuses),
-            _stream_handle(stream))
-
-    def prepare(self, dictionaries: Sequence[bytes], device="cuda"):
-        """-> (blobs, statuses): blob i at ``blobs.ptrs[i]`` (16-byte aligned, ``blobs.sizes[i]`` bytes), status i
-        hipcompSuccess or why dictionary i has no valid blob."""
-        dicts = from_host_chunks(dictionaries, device)
-        sizes = [self.prepared_size(len(d)) for d in dictionaries]
-        blobs = alloc_batch(dicts.n, max(sizes, default=16), device)
-        blobs.sizes = torch.tensor(sizes, dtype=torch.int64, device=device)
-        statuses = torch.full((dicts.n,), -1, dtype=torch.int32, device=device)
-        _check(self.prepare_async(dicts, blobs, blobs.sizes, statuses), "hipcompBatchedZstdDictCompressPrepareAsync")
-        return blobs, statuses
-
     def compress_async(self, src: ChunkBatch, max_chunk: int, temp: Optional[torch.Tensor], dst: ChunkBatch,
                        prepared: torch.Tensor, stream=None) -> int:
-        return self._f("CompressAsync")(
-            _ptr(src.ptrs), _ptr(src.sizes), max_chunk, src.n,
-            _ptr(temp), 0 if temp is None else temp.numel(),
-            _ptr(dst.ptrs), _ptr(dst.sizes), _ptr(prepared), self.opts, _stream_handle(stream))
+        return super().compress_async(src, max_chunk, temp, dst, stream, _ptr(prepared))
 
     def compress(self, src: ChunkBatch, prepared: torch.Tensor, max_chunk: Optional[int] = None) -> ChunkBatch:
-        real_max = int(src.sizes.max().item()) if src.n else 0
-        if max_chunk is None:
-            max_chunk = real_max
-        if max_chunk < real_max:
-            raise ValueError(f"max_chunk {max_chunk} is smaller than the largest chunk of the batch ({real_max} bytes)")
-        dst = alloc_batch(src.n, self.max_output_chunk_size(max_chunk), src.device)
-        temp = _temp(self.compress_temp_size(src.n, max_chunk), src.device)
-        _check(self.compress_async(src, max_chunk, temp, dst, prepared), self._cname("CompressAsync"))
-        return dst
+        return super().compress(src, max_chunk, prepared)

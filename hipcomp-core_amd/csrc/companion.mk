@@ -4,7 +4,6 @@
 #   NAME     the directory under csrc/ and the library's suffix; the sources are $(NAME)_kernels.hip and
 #            $(NAME)_batch.cpp, the exports $(NAME)/exports.map
 #   INCDIRS  further include directories, after the directory's own
-#   HDRS     further headers that every object depends on
 #   DEPLIBS, LDLIBS  (gzip only) libraries it links: the files to wait for, and the link flags
 HIPCC    ?= /opt/rocm/bin/hipcc
 ARCH     ?= gfx950
@@ -17,24 +16,24 @@ CXXFLAGS := -std=c++17 -O3 -fPIC -I$(ROOT)/include -I$(CSRC) -I$(SRCDIR) $(addpr
             -Wall -Wno-unused-function -fno-strict-aliasing $(EXTRA)
 
 OBJS     := $(OBJDIR)/$(NAME)_kernels.hip.o $(OBJDIR)/$(NAME)_batch.cpp.o
-HDRS     := $(wildcard $(SRCDIR)/*.hpp) $(HDRS) $(CSRC)/wave_utils.hpp $(CSRC)/host_common.hpp \
-            $(ROOT)/include/hipcomp.h $(ROOT)/include/hipcomp/shared_types.h $(ROOT)/include/hipcomp/$(NAME).h
 
 all: $(OUTDIR)/libhipcomp_$(NAME).so
 
 # As in ./Makefile: the device assembly of the very object that ships is kept and has to pass the hazard
-# check before the object is accepted.
-$(OBJDIR)/%.hip.o: $(SRCDIR)/%.hip $(HDRS) $(CSRC)/check_asm_hazards.py
+# check before the object is accepted.  The headers an object depends on are those the compiler read for it,
+# written next to it as a .d file (named for the final object, not the one in _temps) and included below.
+$(OBJDIR)/%.hip.o: $(SRCDIR)/%.hip $(CSRC)/check_asm_hazards.py
 	@mkdir -p $(OBJDIR)/$*_temps
-	$(HIPCC) $(CXXFLAGS) --offload-arch=$(ARCH) -save-temps=obj -c $< -o $(OBJDIR)/$*_temps/$*.hip.o
+	$(HIPCC) $(CXXFLAGS) --offload-arch=$(ARCH) -save-temps=obj -MMD -MP -MT $@ -MF $(OBJDIR)/$*.hip.d \
+	    -c $< -o $(OBJDIR)/$*_temps/$*.hip.o
 	python3 $(CSRC)/check_asm_hazards.py $(OBJDIR)/$*_temps/$*-hip-amdgcn-amd-amdhsa-$(ARCH).s
 	cp $(OBJDIR)/$*_temps/$*-hip-amdgcn-amd-amdhsa-$(ARCH).s $(OBJDIR)/$*.$(ARCH).s
 	mv $(OBJDIR)/$*_temps/$*.hip.o $@
 	rm -rf $(OBJDIR)/$*_temps
 
-$(OBJDIR)/%.cpp.o: $(SRCDIR)/%.cpp $(HDRS)
+$(OBJDIR)/%.cpp.o: $(SRCDIR)/%.cpp
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(CXXFLAGS) -x hip --offload-arch=$(ARCH) -c $< -o $@
+	$(HIPCC) $(CXXFLAGS) -x hip --offload-arch=$(ARCH) -MMD -MP -MT $@ -MF $(OBJDIR)/$*.cpp.d -c $< -o $@
 
 $(OUTDIR)/libhipcomp_$(NAME).so: $(OBJS) $(SRCDIR)/exports.map $(DEPLIBS)
 	@mkdir -p $(OUTDIR)
@@ -44,3 +43,5 @@ clean:
 	rm -rf $(OBJDIR) $(OUTDIR)/libhipcomp_$(NAME).so
 
 .PHONY: all clean
+
+-include $(OBJS:.o=.d)

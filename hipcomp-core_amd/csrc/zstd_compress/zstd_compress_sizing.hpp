@@ -1,9 +1,10 @@
 // zstd_compress_sizing.hpp -- the temp-space formula of the Zstandard encoder, free of HIP: the C ABI's size query
 // and the launch (zstd_compress_launch.hpp) use these functions, tests/zstd_codes_driver.cpp prints them for the CPU
-// tests.
+// tests.  Also the check of the options that the entry points of both Zstandard encoders make.
 #pragma once
 
 #include <cstdint>
+#include <string>
 
 #include "zstd_codes.hpp"
 
@@ -33,6 +34,20 @@ constexpr uint64_t enc_temp_bytes_per_wave(uint64_t max_chunk_bytes)
 constexpr uint64_t enc_temp_bytes(uint64_t num_chunks, uint64_t max_chunk_bytes)
 {
   return enc_waves_for(num_chunks) * enc_temp_bytes_per_wave(max_chunk_bytes);
+}
+
+// What an entry point of zstd_compress_batch.cpp or ../zstd_dict_compress/zstd_dict_compress_batch.cpp refuses in its
+// format_opts and chunk size, as the text for its stderr line; empty where it refuses nothing.  `limit` is the
+// library's HIPCOMP_..._MAX_CHUNK_BYTES.
+inline std::string enc_opts_error(int level, int checksum, uint64_t max_chunk_bytes, uint64_t limit)
+{
+  if (level != 0)
+    return "'format_opts.level' must be 0.";
+  if (checksum != 0 && checksum != 1)
+    return "'format_opts.checksum' must be 0 or 1.";
+  if (max_chunk_bytes > limit)
+    return "the chunk size must not exceed " + std::to_string(limit) + " bytes.";
+  return {};
 }
 
 } // namespace zstd

@@ -14,21 +14,13 @@ using namespace hcamd;
 
 namespace {
 
+// (the check that both Zstandard encoders make, zstd_compress_sizing.hpp, with this library's limit)
 bool opts_ok(const char* fn, hipcompBatchedZstdOpts_t opts, size_t max_chunk_bytes, hipcompStatus_t& st)
 {
-  if (opts.level != 0) {
-    st = fail(fn, "'format_opts.level' must be 0.");
-    return false;
-  }
-  if (opts.checksum != 0 && opts.checksum != 1) {
-    st = fail(fn, "'format_opts.checksum' must be 0 or 1.");
-    return false;
-  }
-  if (max_chunk_bytes > HIPCOMP_ZSTD_DICT_COMPRESS_MAX_CHUNK_BYTES) {
-    st = fail(fn, "the chunk size must not exceed 32768 bytes.");
-    return false;
-  }
-  return true;
+  const std::string bad = zstd::enc_opts_error(opts.level, opts.checksum, max_chunk_bytes, HIPCOMP_ZSTD_DICT_COMPRESS_MAX_CHUNK_BYTES);
+  if (!bad.empty())
+    st = fail(fn, bad);
+  return bad.empty();
 }
 
 static_assert(HIPCOMP_ZSTD_DICT_COMPRESS_MAX_CHUNK_BYTES == zstd::kDictEncMaxChunk, "the header's limit");
