@@ -18,6 +18,7 @@
 #include "checksum_launch.hpp"
 #include "hlif_container.hpp"
 #include "host_common.hpp"
+#include "lz4_frame_launch.hpp"
 #include "lz4_launch.hpp"
 #include "range_launch.hpp"
 #include "snappy_launch.hpp"
@@ -716,6 +717,199 @@ struct Core
     check(hipGetLastError(), "decompress_range kernels");
   }
 
+  // ---- LZ4 frames (hipcomp/lz4.hpp; the format: lz4_frame.hpp; the kernels: lz4_frame_launch.hpp) ----
+  // Both directions work in passes of as many blocks as fit the scratch space scratch_bytes() promises, like
+  // decompress_range; the manager's own scratch is as large as the call at hand needs, up to that.
+  // Writing, a pass of P chunks: the frame cursor (16 bytes), six lists (44 bytes per chunk), a slot per chunk for
+  // the batched encoder (unplaced: the frame wants the blocks in chunk order and the stored ones from the input),
+  // the encoder's temp space.
+  size_t frame_write_bytes(size_t P) const { return 16 + 16 + 44 * P + 16 + P * slot_bytes + 16 + lz4_temp_bytes(P); }
+  size_t frame_write_pass(size_t chunks) const
+  {
+    const size_t room = scratch_bytes();
+    size_t P = chunks < kPlacedSlab ? (chunks ? chunks : 1) : kPlacedSlab;
+    if (frame_write_bytes(P) <= room)
+      return P;
+    size_t lo = 1; // (fits: scratch_bytes() holds a slot per resident wave and a full pass's lists)
+    while (lo < P) {
+      const size_t mid = lo + (P - lo + 1) / 2;
+      if (frame_write_bytes(mid) <= room)
+        lo = mid;
+      else
+        P = mid - 1;
+    }
+    return lo;
+  }
+  // Reading, a pass of P blocks: the walk's state (128 bytes), the batched decoder's ticket words (64), the entry lists.
+  static constexpr size_t kFrameReadFixed = 16 + 128 + 64;
+  size_t frame_read_bytes(size_t P) const { return kFrameReadFixed + lz4f::kReadEntryBytes * P; }
+  size_t frame_read_pass(size_t blocks) const
+  {
+    size_t P = (scratch_bytes() - kFrameReadFixed) / lz4f::kReadEntryBytes;
+    P = P < kPlacedSlab ? P : kPlacedSlab;
+    return blocks < P ? (blocks ? blocks : 1) : P;
+  }
+  static lz4f::ReadLists frame_read_lists(uint8_t* at, size_t P)
+  {
+    lz4f::ReadLists l;
+    l.comp_ptrs = reinterpret_cast<const uint8_t**>(at);
+    l.comp_bytes = reinterpret_cast<size_t*>(at + 8 * P);
+    l.batch_bytes = reinterpret_cast<size_t*>(at + 16 * P);
+    l.sizes = reinterpret_cast<size_t*>(at + 24 * P);
+    l.out_ptrs = reinterpret_cast<uint8_t**>(at + 32 * P);
+    l.caps = reinterpret_cast<size_t*>(at + 40 * P);
+    l.batch_caps = reinterpret_cast<size_t*>(at + 48 * P);
+    l.actual = reinterpret_cast<size_t*>(at + 56 * P);
+    l.aux = reinterpret_cast<uint64_t*>(at + 64 * P);
+    l.flags = reinterpret_cast<uint32_t*>(at + 72 * P);
+    l.head = reinterpret_cast<int32_t*>(at + 76 * P);
+    l.statuses = reinterpret_cast<hipcompStatus_t*>(at + 80 * P);
+    return l;
+  }
+
+  hipcomp::CompressionConfig configure_frame_compression(size_t decomp_buffer_size) const
+  {
+    hipcomp::CompressionConfig c(decomp_buffer_size);
+    if (lz4f::code_for_chunk(chunk_bytes) == 0) { // no block maximum of the format holds a chunk
+      *c.get_status() = hipcompErrorInvalidValue;
+      return c;
+    }
+    c.num_chunks = (decomp_buffer_size + chunk_bytes - 1) / chunk_bytes;
+    c.max_compressed_buffer_size = (size_t)lz4f::frame_bound(c.num_chunks, chunk_bytes, computes());
+    return c;
+  }
+
+  void compress_frame(const uint8_t* decomp_buffer, uint8_t* frame, const hipcomp::CompressionConfig& cfg, size_t* frame_bytes)
+  {
+    if (reinterpret_cast<uintptr_t>(frame_bytes) & 7)
+      throw std::runtime_error("compress_frame: frame_bytes must be 8-byte aligned");
+    const uint32_t code = lz4f::code_for_chunk(chunk_bytes);
+    if (code == 0) {
+      set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
+      check(lz4f::launch_set_size(frame_bytes, 0, stream), "compress_frame");
+      return;
+    }
+    const size_t n = cfg.num_chunks;
+    const size_t P = frame_write_pass(n);
+    uint8_t* const s = checksum_area(ensure_scratch(frame_write_bytes(P)));
+    unsigned long long* const cursor = reinterpret_cast<unsigned long long*>(s);
+    uint8_t* const lists = s + 16;
+    lz4f::WriteLists l;
+    l.in_ptrs = reinterpret_cast<const uint8_t**>(lists);
+    l.in_bytes = reinterpret_cast<size_t*>(lists + 8 * P);
+    l.slots = reinterpret_cast<uint8_t**>(lists + 16 * P);
+    l.stream_bytes = reinterpret_cast<size_t*>(lists + 24 * P);
+    l.offsets = reinterpret_cast<uint64_t*>(lists + 32 * P);
+    l.sums = reinterpret_cast<uint32_t*>(lists + 40 * P);
+    uint8_t* const slots = checksum_area(lists + 44 * P);
+    uint8_t* const temp = checksum_area(slots + P * slot_bytes);
+    const bool sums = computes();
+    set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
+    check(lz4f::launch_write_header(frame, cfg.uncompressed_buffer_size, code, sums, cursor, stream), "compress_frame: header");
+    for (size_t first = 0; first < n; first += P) {
+      const uint32_t count = (uint32_t)(n - first < P ? n - first : P);
+      check(lz4f::launch_write_lists(decomp_buffer, cfg.uncompressed_buffer_size, chunk_bytes, first, count, slots, slot_bytes,
+                                     l, stream),
+            "compress_frame: chunk lists");
+      check(lz4_launch_compress(l.in_ptrs, l.in_bytes, l.slots, l.stream_bytes, ht_size, count, lz4_elem, temp,
+                                lz4_temp_bytes(P), chunk_bytes, lz4_mode_from_environment(), stream, nullptr),
+            "LZ4Manager::compress_frame");
+      check(lz4f::launch_write_scan(l, count, sums, cursor, stream), "compress_frame: scan");
+      if (sums)
+        check(lz4f::launch_write_sums(l, count, stream), "compress_frame: block checksums");
+      check(lz4f::launch_write_blocks(frame, l, count, chunk_bytes, sums, stream), "compress_frame: blocks");
+    }
+    check(lz4f::launch_write_end(frame, cursor, frame_bytes, stream), "compress_frame: end mark");
+    check(hipGetLastError(), "compress_frame kernels");
+  }
+
+  // the entries of one pass: the walk, the sizes (the batched decoder's parse-only pass; the token walk for linked
+  // frames), the scan that places them
+  void frame_pass_lists(const uint8_t* frames, size_t frames_bytes, lz4f::ReadState* st, const lz4f::ReadLists& l,
+                        uint32_t count, void* ticket, uint8_t* out, uint64_t out_bytes)
+  {
+    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, count, verifies(), stream), "frame: walk");
+    check(lz4f::launch_read_linked_sizes(l, st, count, stream), "frame: sizes");
+    check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, nullptr, count, nullptr, l.actual, nullptr, false, stream,
+                                ticket, 64),
+          "frame: sizes");
+    check(lz4f::launch_read_scan(l, st, count, out, out_bytes, stream), "frame: scan");
+  }
+
+  hipcomp::DecompressionConfig configure_frame_decompression(const uint8_t* frames, size_t frames_bytes)
+  {
+    hipcomp::DecompressionConfig d;
+    uint8_t* s = checksum_area(ensure_scratch(frame_read_bytes(1)));
+    lz4f::ReadState* st = reinterpret_cast<lz4f::ReadState*>(s);
+    lz4f::ReadState h;
+    auto fetch = [&] {
+      check(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, stream), "configure_frame_decompression");
+      check(hipStreamSynchronize(stream), "configure_frame_decompression");
+    };
+    check(lz4f::launch_read_reset(st, stream), "configure_frame_decompression");
+    check(lz4f::launch_read_walk(frames, frames_bytes, st, nullptr, 0, false, stream), "configure_frame_decompression");
+    fetch();
+    if (h.reason != lz4f::kOk) {
+      *d.get_status() = (hipcompStatus_t)lz4f::status_of(h.reason);
+      return d;
+    }
+    d.num_chunks = (uint32_t)h.blocks;
+    if (h.all_declared) {
+      d.decomp_data_size = (size_t)h.declared_sum;
+      return d;
+    }
+    // a frame does not say: the sizes are those the blocks parse to
+    const size_t blocks = (size_t)h.blocks, P = frame_read_pass(blocks);
+    s = checksum_area(ensure_scratch(frame_read_bytes(P)));
+    st = reinterpret_cast<lz4f::ReadState*>(s);
+    const lz4f::ReadLists l = frame_read_lists(s + 128 + 64, P);
+    check(lz4f::launch_read_reset(st, stream), "configure_frame_decompression");
+    for (size_t first = 0; first < blocks; first += P) {
+      const uint32_t count = (uint32_t)(blocks - first < P ? blocks - first : P);
+      frame_pass_lists(frames, frames_bytes, st, l, count, s + 128, nullptr, ~uint64_t(0));
+    }
+    fetch();
+    d.decomp_data_size = (size_t)h.out_cursor;
+    return d;
+  }
+
+  void decompress_frame(uint8_t* decomp_buffer, const uint8_t* frames, size_t frames_bytes,
+                        const hipcomp::DecompressionConfig& cfg)
+  {
+    // (a configuration refused by configure_frame_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() != hipcompSuccess)
+      return;
+    const size_t blocks = cfg.num_chunks, P = frame_read_pass(blocks);
+    uint8_t* const s = checksum_area(ensure_scratch(frame_read_bytes(P)));
+    lz4f::ReadState* const st = reinterpret_cast<lz4f::ReadState*>(s);
+    void* const ticket = s + 128;
+    const lz4f::ReadLists l = frame_read_lists(s + 128 + 64, P);
+    check(lz4f::launch_read_reset(st, stream), "decompress_frame");
+    for (size_t first = 0; first < blocks; first += P) {
+      const uint32_t count = (uint32_t)(blocks - first < P ? blocks - first : P);
+      frame_pass_lists(frames, frames_bytes, st, l, count, ticket, decomp_buffer, cfg.decomp_data_size);
+      check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, true,
+                                  stream, ticket, 64),
+            "LZ4Manager::decompress_frame");
+      check(lz4f::launch_read_verdict(l, st, count, stream), "decompress_frame: verdict");
+      // (workgroups per stored block by the size of the average block: the sizes themselves are on the device)
+      check(lz4f::launch_read_stored(l, st, count, 2 * (uint64_t)(cfg.decomp_data_size / blocks), stream),
+            "decompress_frame: stored blocks");
+      check(lz4f::launch_read_linked(l, st, count, decomp_buffer, stream), "decompress_frame: linked blocks");
+      if (verifies()) {
+        check(lz4f::launch_read_block_sums(l, st, count, stream), "decompress_frame: block checksums");
+        check(lz4f::launch_read_content_sums(l, st, count, decomp_buffer, stream), "decompress_frame: content checksums");
+      }
+      check(lz4f::launch_read_pass_end(l, st, decomp_buffer, stream), "decompress_frame");
+    }
+    // what lies behind the last block (trailers are read with their block; skippable and empty frames here)
+    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, 0, verifies(), stream), "decompress_frame: walk");
+    check(lz4f::launch_read_finish(st, blocks, cfg.decomp_data_size, policy == hipcomp::ComputeAndVerify, cfg.get_status(),
+                                   stream),
+          "decompress_frame");
+    check(hipGetLastError(), "decompress_frame kernels");
+  }
+
   void set_scratch_buffer(uint8_t* new_scratch_buffer)
   {
     if (own_scratch)
@@ -825,6 +1019,19 @@ LZ4Manager::LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStr
   impl->core.set_policy(checksum_policy);
 }
 HCAMD_MANAGER_METHODS(LZ4Manager)
+CompressionConfig LZ4Manager::configure_frame_compression(size_t n) { return impl->core.configure_frame_compression(n); }
+void LZ4Manager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
+{
+  impl->core.compress_frame(in, frame, c, frame_bytes);
+}
+DecompressionConfig LZ4Manager::configure_frame_decompression(const uint8_t* frames, size_t frames_bytes)
+{
+  return impl->core.configure_frame_decompression(frames, frames_bytes);
+}
+void LZ4Manager::decompress_frame(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const DecompressionConfig& c)
+{
+  impl->core.decompress_frame(out, frames, frames_bytes, c);
+}
 
 SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, int device_id)
 {

@@ -6,6 +6,7 @@
 // checksum, 4] }* | end mark 0 | [content checksum, 4].  HC is the second byte
 // of the XXH32 (seed 0) of the descriptor bytes from FLG on.
 #include "host_common.hpp"
+#include "xxh32_math.hpp"
 
 #include "hipcomp/lz4_interop.h"
 
@@ -17,33 +18,9 @@ constexpr uint32_t kMagic = 0x184D2204u;
 
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// XXH32 (public algorithm, xxHash specification), only ever run on the few
-// descriptor bytes of a frame header
-uint32_t xxh32(const uint8_t* p, size_t len, uint32_t seed)
-{
-  const uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
-  const uint8_t* const end = p + len;
-  uint32_t h;
-  if (len >= 16) {
-    uint32_t v1 = seed + P1 + P2, v2 = seed + P2, v3 = seed, v4 = seed - P1;
-    do {
-      v1 = rotl(v1 + rd32(p) * P2, 13) * P1; p += 4;
-      v2 = rotl(v2 + rd32(p) * P2, 13) * P1; p += 4;
-      v3 = rotl(v3 + rd32(p) * P2, 13) * P1; p += 4;
-      v4 = rotl(v4 + rd32(p) * P2, 13) * P1; p += 4;
-    } while (p + 16 <= end);
-    h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-  } else {
-    h = seed + P5;
-  }
-  h += (uint32_t)len;
-  while (p + 4 <= end) { h = rotl(h + rd32(p) * P3, 17) * P4; p += 4; }
-  while (p < end) { h = rotl(h + *p * P5, 11) * P1; ++p; }
-  h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
-  return h;
-}
+// XXH32: xxh32_math.hpp, the one copy (the device path of the LZ4 manager hashes with it too); here only ever
+// run on the few descriptor bytes of a frame header
+uint32_t xxh32(const uint8_t* p, size_t len, uint32_t seed) { return hcamd::xxh32::hash(p, len, seed); }
 
 const size_t kBlockSizes[8] = {0, 0, 0, 0, 64u << 10, 256u << 10, 1u << 20, 4u << 20};
 

@@ -17,6 +17,10 @@
  * blocks, no block / content checksums, content size present; frames read: any
  * frame whose blocks are independent (block checksums are skipped, a content
  * checksum is ignored, uncompressed blocks are reported as such).
+ *
+ * The device path is the LZ4 manager's (hipcomp/lz4.hpp, C++): compress_frame /
+ * decompress_frame write and read frames on device buffers, linked blocks,
+ * stored blocks and checksums included, with no copy to the host.
  */
 #ifndef HIPCOMP_LZ4_INTEROP_H
 #define HIPCOMP_LZ4_INTEROP_H
