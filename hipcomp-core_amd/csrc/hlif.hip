@@ -21,6 +21,7 @@
 #include "lz4_frame_launch.hpp"
 #include "lz4_launch.hpp"
 #include "range_launch.hpp"
+#include "snappy_frame_launch.hpp"
 #include "snappy_launch.hpp"
 #include "wave_utils.hpp"
 
@@ -910,6 +911,151 @@ struct Core
     check(hipGetLastError(), "decompress_frame kernels");
   }
 
+  // ---- Snappy framed streams (hipcomp/snappy.hpp; the format: snappy_frame.hpp; the kernels: snappy_frame_launch.hpp;
+  // DESIGN.md 21) ----
+  // Passes of as many chunks as fit the scratch space scratch_bytes() promises, like the LZ4 frames above.
+  // Writing, a pass of P chunks: the stream cursor (16 bytes), six lists, a slot per chunk for the batched encoder
+  // (unplaced: the stream wants the chunks in order and the stored ones from the input).
+  size_t sz_write_bytes(size_t P) const { return 16 + 16 + szf::kWriteEntryBytes * P + 16 + P * slot_bytes; }
+  size_t sz_write_pass(size_t chunks) const
+  {
+    const size_t room = scratch_bytes();
+    size_t P = chunks < kPlacedSlab ? (chunks ? chunks : 1) : kPlacedSlab;
+    if (sz_write_bytes(P) <= room)
+      return P;
+    size_t lo = 1; // (fits: scratch_bytes() holds a slot per resident wave and a full pass's lists)
+    while (lo < P) {
+      const size_t mid = lo + (P - lo + 1) / 2;
+      if (sz_write_bytes(mid) <= room)
+        lo = mid;
+      else
+        P = mid - 1;
+    }
+    return lo;
+  }
+  // Reading, a pass of P chunks: the walk's state (128 bytes), the entry lists.
+  static constexpr size_t kSzReadFixed = 16 + 128;
+  size_t sz_read_bytes(size_t P) const { return kSzReadFixed + szf::kReadEntryBytes * P; }
+  size_t sz_read_pass(size_t chunks) const
+  {
+    size_t P = (scratch_bytes() - kSzReadFixed) / szf::kReadEntryBytes;
+    P = P < kPlacedSlab ? P : kPlacedSlab;
+    return chunks < P ? (chunks ? chunks : 1) : P;
+  }
+  static szf::ReadLists sz_read_lists(uint8_t* at, size_t P)
+  {
+    szf::ReadLists l;
+    l.payloads = reinterpret_cast<const uint8_t**>(at);
+    l.batch_bytes = reinterpret_cast<size_t*>(at + 8 * P);
+    l.out_ptrs = reinterpret_cast<uint8_t**>(at + 16 * P);
+    l.batch_caps = reinterpret_cast<size_t*>(at + 24 * P);
+    l.actual = reinterpret_cast<size_t*>(at + 32 * P);
+    l.content = reinterpret_cast<uint32_t*>(at + 40 * P);
+    l.crcs = reinterpret_cast<uint32_t*>(at + 44 * P);
+    l.flags = reinterpret_cast<uint32_t*>(at + 48 * P);
+    l.statuses = reinterpret_cast<hipcompStatus_t*>(at + 52 * P);
+    return l;
+  }
+
+  hipcomp::CompressionConfig sz_configure_compression(size_t decomp_buffer_size) const
+  {
+    hipcomp::CompressionConfig c(decomp_buffer_size);
+    if (chunk_bytes > szf::kMaxContent) { // no data chunk of the format holds a chunk
+      *c.get_status() = hipcompErrorInvalidValue;
+      return c;
+    }
+    c.num_chunks = (decomp_buffer_size + chunk_bytes - 1) / chunk_bytes;
+    c.max_compressed_buffer_size = (size_t)szf::frame_bound(c.num_chunks, chunk_bytes);
+    return c;
+  }
+
+  void sz_compress(const uint8_t* decomp_buffer, uint8_t* frame, const hipcomp::CompressionConfig& cfg, size_t* frame_bytes)
+  {
+    if (reinterpret_cast<uintptr_t>(frame_bytes) & 7)
+      throw std::runtime_error("compress_frame: frame_bytes must be 8-byte aligned");
+    if (chunk_bytes > szf::kMaxContent) {
+      set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
+      check(szf::launch_set_size(frame_bytes, 0, stream), "compress_frame");
+      return;
+    }
+    const size_t n = cfg.num_chunks;
+    const size_t P = sz_write_pass(n);
+    uint8_t* const s = checksum_area(ensure_scratch(sz_write_bytes(P)));
+    unsigned long long* const cursor = reinterpret_cast<unsigned long long*>(s);
+    uint8_t* const lists = s + 16;
+    szf::WriteLists l;
+    l.in_ptrs = reinterpret_cast<const uint8_t**>(lists);
+    l.in_bytes = reinterpret_cast<size_t*>(lists + 8 * P);
+    l.slots = reinterpret_cast<uint8_t**>(lists + 16 * P);
+    l.block_bytes = reinterpret_cast<size_t*>(lists + 24 * P);
+    l.offsets = reinterpret_cast<uint64_t*>(lists + 32 * P);
+    l.crcs = reinterpret_cast<uint32_t*>(lists + 40 * P);
+    uint8_t* const slots = checksum_area(lists + szf::kWriteEntryBytes * P);
+    set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
+    check(szf::launch_write_begin(frame, cursor, stream), "compress_frame: identifier");
+    for (size_t first = 0; first < n; first += P) {
+      const uint32_t count = (uint32_t)(n - first < P ? n - first : P);
+      check(szf::launch_write_lists(decomp_buffer, cfg.uncompressed_buffer_size, chunk_bytes, first, count, slots, slot_bytes,
+                                    l, stream),
+            "compress_frame: chunk lists");
+      snappy_launch_compress(l.in_ptrs, l.in_bytes, l.slots, l.block_bytes, count, stream);
+      check(hipGetLastError(), "SnappyManager::compress_frame");
+      // (the CRC is part of the format: computed under every ChecksumPolicy)
+      check(szf::launch_write_crcs(l, count, stream), "compress_frame: checksums");
+      check(szf::launch_write_scan(l, count, cursor, stream), "compress_frame: scan");
+      check(szf::launch_write_chunks(frame, l, count, chunk_bytes, stream), "compress_frame: chunks");
+    }
+    check(szf::launch_write_end(cursor, frame_bytes, stream), "compress_frame: length");
+    check(hipGetLastError(), "compress_frame kernels");
+  }
+
+  hipcomp::DecompressionConfig sz_configure_decompression(const uint8_t* frames, size_t frames_bytes)
+  {
+    hipcomp::DecompressionConfig d;
+    szf::ReadState* const st = reinterpret_cast<szf::ReadState*>(checksum_area(ensure_scratch(sz_read_bytes(1))));
+    szf::ReadState h;
+    check(szf::launch_read_reset(st, stream), "configure_frame_decompression");
+    check(szf::launch_read_walk(frames, frames_bytes, st, nullptr, 0, stream), "configure_frame_decompression");
+    check(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, stream), "configure_frame_decompression");
+    check(hipStreamSynchronize(stream), "configure_frame_decompression");
+    if (h.reason != szf::kOk || h.chunks > 0xFFFFFFFFull) {
+      *d.get_status() = hipcompErrorCannotDecompress;
+      return d;
+    }
+    d.num_chunks = (uint32_t)h.chunks;
+    d.decomp_data_size = (size_t)h.content;
+    return d;
+  }
+
+  void sz_decompress(uint8_t* decomp_buffer, const uint8_t* frames, size_t frames_bytes, const hipcomp::DecompressionConfig& cfg)
+  {
+    // (a configuration refused by configure_frame_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() != hipcompSuccess)
+      return;
+    const size_t chunks = cfg.num_chunks, P = sz_read_pass(chunks);
+    uint8_t* const s = checksum_area(ensure_scratch(sz_read_bytes(P)));
+    szf::ReadState* const st = reinterpret_cast<szf::ReadState*>(s);
+    const szf::ReadLists l = sz_read_lists(s + 128, P);
+    check(szf::launch_read_reset(st, stream), "decompress_frame");
+    if (chunks == 0) // identifiers and padding at the most
+      check(szf::launch_read_walk(frames, frames_bytes, st, &l, 0, stream), "decompress_frame: walk");
+    for (size_t first = 0; first < chunks; first += P) {
+      const uint32_t count = (uint32_t)(chunks - first < P ? chunks - first : P);
+      check(szf::launch_read_walk(frames, frames_bytes, st, &l, count, stream), "decompress_frame: walk");
+      check(szf::launch_read_scan(l, st, decomp_buffer, cfg.decomp_data_size, stream), "decompress_frame: scan");
+      snappy_launch_decompress(l.payloads, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, stream);
+      check(hipGetLastError(), "SnappyManager::decompress_frame");
+      check(szf::launch_read_verdict(l, st, count, stream), "decompress_frame: verdict");
+      // (workgroups per stored chunk by the size of the average chunk: the sizes themselves are on the device)
+      check(szf::launch_read_stored(l, st, count, 2 * (uint64_t)(cfg.decomp_data_size / chunks), stream),
+            "decompress_frame: stored chunks");
+      if (verifies())
+        check(szf::launch_read_crcs(l, st, count, stream), "decompress_frame: checksums");
+    }
+    check(szf::launch_read_finish(st, chunks, cfg.decomp_data_size, cfg.get_status(), stream), "decompress_frame");
+    check(hipGetLastError(), "decompress_frame kernels");
+  }
+
   void set_scratch_buffer(uint8_t* new_scratch_buffer)
   {
     if (own_scratch)
@@ -1052,6 +1198,19 @@ SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, 
   impl->core.set_policy(checksum_policy);
 }
 HCAMD_MANAGER_METHODS(SnappyManager)
+CompressionConfig SnappyManager::configure_frame_compression(size_t n) { return impl->core.sz_configure_compression(n); }
+void SnappyManager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
+{
+  impl->core.sz_compress(in, frame, c, frame_bytes);
+}
+DecompressionConfig SnappyManager::configure_frame_decompression(const uint8_t* frames, size_t frames_bytes)
+{
+  return impl->core.sz_configure_decompression(frames, frames_bytes);
+}
+void SnappyManager::decompress_frame(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const DecompressionConfig& c)
+{
+  impl->core.sz_decompress(out, frames, frames_bytes, c);
+}
 
 // Every chunk of the container is one partition of the batched Cascaded codec, cut into the
 // reference's 4096-byte sub-chunks whatever options.chunk_size says (that is the CONTAINER's

@@ -38,6 +38,44 @@ struct SnappyManager : hipcompManagerBase
   void decompress_range(uint8_t* out, const uint8_t* comp_buffer, const DecompressionConfig& decomp_config,
                         size_t first_byte, size_t num_bytes);
 
+  /* ---- Snappy framed streams (magic ff 06 00 00 "sNaPpY": .sz files, Go's snappy.Writer / Reader, snzip,
+     python-snappy's stream classes) on the device ----
+     All buffers are device-accessible and may lie at any byte alignment; all four methods work on the manager's
+     stream and only configure_frame_decompression synchronises it; the status goes to cfg.get_status();
+     get_required_scratch_buffer_size() is what it was (a pass takes as many chunks as fit).  INTEGRATION.md,
+     "Snappy framed streams in the Snappy manager", has the contract in full.  C++ only: no C or Python binding.
+
+     Writing: one stream: the identifier, then one data chunk per manager chunk in chunk order -- type 0x00 with
+     exactly the block hipcompBatchedSnappyCompressAsync writes for the chunk where that is strictly shorter than
+     the chunk, else type 0x01 with the chunk itself.  Every data chunk carries the masked CRC-32C of its
+     uncompressed bytes, computed on the device under every ChecksumPolicy: it is part of the format.  0 bytes give
+     the 10-byte identifier alone.  cfg.max_compressed_buffer_size = 10 + num_chunks * (uncomp_chunk_size + 8) (the
+     last chunk counted whole); nothing is written at or beyond it.  *frame_bytes (one device-accessible, 8-byte
+     aligned word, written on the stream) is the exact length.  uncomp_chunk_size > 65536, the most a data chunk
+     holds: the configuration has hipcompErrorInvalidValue and sizes 0, compress_frame launches nothing but
+     *frame_bytes = 0. */
+  CompressionConfig configure_frame_compression(size_t decomp_buffer_size);
+  void compress_frame(const uint8_t* decomp_buffer, uint8_t* frame, const CompressionConfig& comp_config,
+                      size_t* frame_bytes);
+  /* Reading: `frames` holds zero or more streams back to back, written by anyone: compressed and uncompressed data
+     chunks of up to 65536 bytes of content, repeated identifiers, padding (0xfe) and reserved skippable chunks
+     (0x80 - 0xfd) anywhere.  The configuration holds the sum of the stored lengths and of the compressed chunks'
+     length preambles, and the number of data chunks.  hipcompErrorCannotDecompress: a first chunk that is not the
+     identifier, an identifier of another length or body, a reserved unskippable type (0x02 - 0x7f), a header or body
+     that runs past frames_bytes, a data chunk without room for its CRC, a compressed chunk without payload, a
+     preamble that is no complete varint of at most 5 bytes or exceeds 65536, an uncompressed chunk of more than
+     65536 bytes -- these configure 0 / 0 with the status set, and decompress_frame then launches nothing -- and,
+     from decompress_frame, a block the batched decoder refuses or that decodes to another size than its preamble.
+     Under a verifying policy a data chunk whose masked CRC does not fit gives hipcompErrorBadChecksum (it wins over
+     CannotDecompress; the CRC of a chunk whose decode failed is not looked at); under the other policies the CRCs
+     are not looked at -- readers elsewhere always check.  Every data chunk carries a CRC, so ComputeAndVerify never
+     reports hipcompErrorCannotVerifyChecksums here.
+     Reads stay inside frames[0, frames_bytes), writes inside decomp_buffer[0, decomp_data_size) and the scratch.
+     The chunk chain is followed by one lane: the format has no index. */
+  DecompressionConfig configure_frame_decompression(const uint8_t* frames, size_t frames_bytes);
+  void decompress_frame(uint8_t* decomp_buffer, const uint8_t* frames, size_t frames_bytes,
+                        const DecompressionConfig& decomp_config);
+
 private:
   struct Impl;
   std::unique_ptr<Impl> impl;
