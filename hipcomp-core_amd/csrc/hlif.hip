@@ -18,6 +18,7 @@
 #include "checksum_launch.hpp"
 #include "hlif_container.hpp"
 #include "host_common.hpp"
+#include "lz4_frame_index_launch.hpp"
 #include "lz4_frame_launch.hpp"
 #include "lz4_launch.hpp"
 #include "range_launch.hpp"
@@ -741,8 +742,15 @@ struct Core
     }
     return lo;
   }
-  // Reading, a pass of P blocks: the walk's state (128 bytes), the batched decoder's ticket words (64), the entry lists.
-  static constexpr size_t kFrameReadFixed = 16 + 128 + 64;
+  // Reading, a pass of P blocks: the walk's state (128 bytes), the batched decoder's ticket words (64), the indexed
+  // read's state (lz4_frame_index_launch.hpp), the entry lists.  The state fills the 2048 bytes to the last one
+  // (128 + 64 + 1856): a larger IndexState needs a larger kFrameReadLists.  The required scratch is what it was, so
+  // a pass of every frame read, indexed or not, holds 1856 / kReadEntryBytes = 22 entries fewer than before the index;
+  // that matters only where the scratch and not kPlacedSlab bounds the pass (chunks of a few bytes).
+  static constexpr size_t kFrameReadLists = 2048;
+  static constexpr size_t kFrameReadFixed = 16 + kFrameReadLists;
+  static_assert(128 + 64 + sizeof(lz4f::IndexState) <= kFrameReadLists, "the indexed read's state does not fit");
+  static lz4f::IndexState* frame_index_state(uint8_t* s) { return reinterpret_cast<lz4f::IndexState*>(s + 128 + 64); }
   size_t frame_read_bytes(size_t P) const { return kFrameReadFixed + lz4f::kReadEntryBytes * P; }
   size_t frame_read_pass(size_t blocks) const
   {
@@ -768,7 +776,8 @@ struct Core
     return l;
   }
 
-  hipcomp::CompressionConfig configure_frame_compression(size_t decomp_buffer_size) const
+  // index: the frame gets its block index in front of it (lz4_frame_index.hpp), 44 + 4 * num_chunks bytes more
+  hipcomp::CompressionConfig configure_frame_compression(size_t decomp_buffer_size, bool index = false) const
   {
     hipcomp::CompressionConfig c(decomp_buffer_size);
     if (lz4f::code_for_chunk(chunk_bytes) == 0) { // no block maximum of the format holds a chunk
@@ -776,21 +785,32 @@ struct Core
       return c;
     }
     c.num_chunks = (decomp_buffer_size + chunk_bytes - 1) / chunk_bytes;
-    c.max_compressed_buffer_size = (size_t)lz4f::frame_bound(c.num_chunks, chunk_bytes, computes());
+    // (a frame of 2^32 blocks or more cannot be indexed: its N is a u32)
+    if (index && c.num_chunks > 0xFFFFFFFFull) {
+      *c.get_status() = hipcompErrorInvalidValue;
+      c.num_chunks = 0;
+      return c;
+    }
+    c.max_compressed_buffer_size = (size_t)lz4f::frame_bound(c.num_chunks, chunk_bytes, computes())
+                                   + (index ? (size_t)lz4f::index_bytes(c.num_chunks) : 0);
     return c;
   }
 
-  void compress_frame(const uint8_t* decomp_buffer, uint8_t* frame, const hipcomp::CompressionConfig& cfg, size_t* frame_bytes)
+  // index: the room of the index is left in front of the frame, its words are written pass by pass from the lists
+  // write_blocks_kernel reads, its hash once they all stand
+  void compress_frame(const uint8_t* decomp_buffer, uint8_t* const buffer, const hipcomp::CompressionConfig& cfg,
+                      size_t* frame_bytes, bool index = false)
   {
     if (reinterpret_cast<uintptr_t>(frame_bytes) & 7)
       throw std::runtime_error("compress_frame: frame_bytes must be 8-byte aligned");
     const uint32_t code = lz4f::code_for_chunk(chunk_bytes);
-    if (code == 0) {
+    if (code == 0 || (index && cfg.num_chunks > 0xFFFFFFFFull)) {
       set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
       check(lz4f::launch_set_size(frame_bytes, 0, stream), "compress_frame");
       return;
     }
     const size_t n = cfg.num_chunks;
+    uint8_t* const frame = buffer + (index ? (size_t)lz4f::index_bytes(n) : 0);
     const size_t P = frame_write_pass(n);
     uint8_t* const s = checksum_area(ensure_scratch(frame_write_bytes(P)));
     unsigned long long* const cursor = reinterpret_cast<unsigned long long*>(s);
@@ -806,6 +826,10 @@ struct Core
     uint8_t* const temp = checksum_area(slots + P * slot_bytes);
     const bool sums = computes();
     set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
+    if (index)
+      check(lz4f::launch_index_write_fields(buffer, (uint32_t)n, (uint32_t)chunk_bytes, cfg.uncompressed_buffer_size, sums,
+                                            stream),
+            "compress_frame: index");
     check(lz4f::launch_write_header(frame, cfg.uncompressed_buffer_size, code, sums, cursor, stream), "compress_frame: header");
     for (size_t first = 0; first < n; first += P) {
       const uint32_t count = (uint32_t)(n - first < P ? n - first : P);
@@ -819,22 +843,48 @@ struct Core
       if (sums)
         check(lz4f::launch_write_sums(l, count, stream), "compress_frame: block checksums");
       check(lz4f::launch_write_blocks(frame, l, count, chunk_bytes, sums, stream), "compress_frame: blocks");
+      if (index)
+        check(lz4f::launch_index_write_words(buffer, l, first, count, stream), "compress_frame: index");
     }
     check(lz4f::launch_write_end(frame, cursor, frame_bytes, stream), "compress_frame: end mark");
+    if (index)
+      check(lz4f::launch_index_write_end(buffer, (uint32_t)n, frame_bytes, stream), "compress_frame: index");
     check(hipGetLastError(), "compress_frame kernels");
   }
 
   // the entries of one pass: the walk, the sizes (the batched decoder's parse-only pass; the token walk for linked
   // frames), the scan that places them
   void frame_pass_lists(const uint8_t* frames, size_t frames_bytes, lz4f::ReadState* st, const lz4f::ReadLists& l,
-                        uint32_t count, void* ticket, uint8_t* out, uint64_t out_bytes)
+                        uint32_t count, void* ticket, uint8_t* out, uint64_t out_bytes, lz4f::IndexState* ix = nullptr)
   {
-    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, count, verifies(), stream), "frame: walk");
+    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, count, verifies(), stream, ix ? &ix->skip : nullptr),
+          "frame: walk");
     check(lz4f::launch_read_linked_sizes(l, st, count, stream), "frame: sizes");
     check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, nullptr, count, nullptr, l.actual, nullptr, false, stream,
                                 ticket, 64),
           "frame: sizes");
     check(lz4f::launch_read_scan(l, st, count, out, out_bytes, stream), "frame: scan");
+  }
+
+  // What configure_frame_decompression found in front of the frames of the buffer it saw last: decompress_frame
+  // does not launch the indexed passes for a buffer that had no index then.  A hint and no more -- the passes
+  // themselves decide on the device, whatever the buffer holds by now.
+  const uint8_t* hint_frames = nullptr;
+  size_t hint_bytes = 0;
+  bool hint_indexed = false;
+  // the state of the last decompress_frame or decompress_frame_range
+  lz4f::ReadState* last_read_state = nullptr;
+
+  // Blocks the chain's walk stepped over in the last decompress_frame or decompress_frame_range (synchronises the
+  // stream): ReadState::walked, which the walk alone adds to, block by block.
+  size_t frame_walked_blocks()
+  {
+    if (!last_read_state)
+      return 0;
+    lz4f::ReadState h;
+    check(hipMemcpyAsync(&h, last_read_state, sizeof(h), hipMemcpyDeviceToHost, stream), "frame_walked_blocks");
+    check(hipStreamSynchronize(stream), "frame_walked_blocks");
+    return (size_t)h.walked;
   }
 
   hipcomp::DecompressionConfig configure_frame_decompression(const uint8_t* frames, size_t frames_bytes)
@@ -847,6 +897,25 @@ struct Core
       check(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, stream), "configure_frame_decompression");
       check(hipStreamSynchronize(stream), "configure_frame_decompression");
     };
+    // indexed frames and nothing else: the numbers are the indexes', every block tested in its place
+    {
+      lz4f::IndexState* const ix = frame_index_state(s);
+      lz4f::IndexState hx;
+      check(lz4f::launch_index_begin(frames, frames_bytes, ix, stream), "configure_frame_decompression: index");
+      check(lz4f::launch_index_list(frames, frames_bytes, ix, st, nullptr, 0, nullptr, 0, stream),
+            "configure_frame_decompression: index");
+      check(hipMemcpyAsync(&hx, ix, offsetof(lz4f::IndexState, frame), hipMemcpyDeviceToHost, stream),
+            "configure_frame_decompression");
+      check(hipStreamSynchronize(stream), "configure_frame_decompression");
+      hint_frames = frames;
+      hint_bytes = frames_bytes;
+      hint_indexed = hx.ok && hx.listed == hx.blocks;
+      if (hint_indexed) {
+        d.num_chunks = (uint32_t)hx.blocks;
+        d.decomp_data_size = (size_t)hx.content_bytes;
+        return d;
+      }
+    }
     check(lz4f::launch_read_reset(st, stream), "configure_frame_decompression");
     check(lz4f::launch_read_walk(frames, frames_bytes, st, nullptr, 0, false, stream), "configure_frame_decompression");
     fetch();
@@ -863,7 +932,7 @@ struct Core
     const size_t blocks = (size_t)h.blocks, P = frame_read_pass(blocks);
     s = checksum_area(ensure_scratch(frame_read_bytes(P)));
     st = reinterpret_cast<lz4f::ReadState*>(s);
-    const lz4f::ReadLists l = frame_read_lists(s + 128 + 64, P);
+    const lz4f::ReadLists l = frame_read_lists(s + kFrameReadLists, P);
     check(lz4f::launch_read_reset(st, stream), "configure_frame_decompression");
     for (size_t first = 0; first < blocks; first += P) {
       const uint32_t count = (uint32_t)(blocks - first < P ? blocks - first : P);
@@ -884,11 +953,37 @@ struct Core
     uint8_t* const s = checksum_area(ensure_scratch(frame_read_bytes(P)));
     lz4f::ReadState* const st = reinterpret_cast<lz4f::ReadState*>(s);
     void* const ticket = s + 128;
-    const lz4f::ReadLists l = frame_read_lists(s + 128 + 64, P);
+    // (no indexed passes for a buffer that had no index when it was configured: the parent's launches, one for one)
+    const bool try_index = !(hint_frames == frames && hint_bytes == frames_bytes && !hint_indexed);
+    lz4f::IndexState* const ix = try_index ? frame_index_state(s) : nullptr;
+    last_read_state = st;
+    const lz4f::ReadLists l = frame_read_lists(s + kFrameReadLists, P);
     check(lz4f::launch_read_reset(st, stream), "decompress_frame");
+    // The indexed passes: entries from the index (no walk, no parse-only pass), the batched decoder, the stored
+    // blocks, the block checksums.  Whether they held is a word on the device: if so the chain's passes below find
+    // nothing to do, if not they start from the reset state and do it all.
+    if (try_index) {
+      check(lz4f::launch_index_begin(frames, frames_bytes, ix, stream), "decompress_frame: index");
+      for (size_t first = 0; first < blocks; first += P) {
+        const uint32_t count = (uint32_t)(blocks - first < P ? blocks - first : P);
+        check(lz4f::launch_index_list(frames, frames_bytes, ix, st, &l, count, decomp_buffer, cfg.decomp_data_size, stream),
+              "decompress_frame: index");
+        check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, true,
+                                    stream, ticket, 64),
+              "LZ4Manager::decompress_frame");
+        check(lz4f::launch_index_verdict(l, st, ix, count, stream), "decompress_frame: index");
+        check(lz4f::launch_read_stored(l, st, count, 2 * (uint64_t)(cfg.decomp_data_size / blocks), stream),
+              "decompress_frame: stored blocks");
+        if (verifies())
+          check(lz4f::launch_read_block_sums(l, st, count, stream), "decompress_frame: block checksums");
+      }
+      check(lz4f::launch_index_end(ix, st, l, (uint32_t)(blocks < P ? blocks : P), frames_bytes, blocks, stream),
+            "decompress_frame: index");
+    }
+    const uint32_t* const skip = ix ? &ix->skip : nullptr;
     for (size_t first = 0; first < blocks; first += P) {
       const uint32_t count = (uint32_t)(blocks - first < P ? blocks - first : P);
-      frame_pass_lists(frames, frames_bytes, st, l, count, ticket, decomp_buffer, cfg.decomp_data_size);
+      frame_pass_lists(frames, frames_bytes, st, l, count, ticket, decomp_buffer, cfg.decomp_data_size, ix);
       check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, true,
                                   stream, ticket, 64),
             "LZ4Manager::decompress_frame");
@@ -904,11 +999,126 @@ struct Core
       check(lz4f::launch_read_pass_end(l, st, decomp_buffer, stream), "decompress_frame");
     }
     // what lies behind the last block (trailers are read with their block; skippable and empty frames here)
-    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, 0, verifies(), stream), "decompress_frame: walk");
+    check(lz4f::launch_read_walk(frames, frames_bytes, st, &l, 0, verifies(), stream, skip), "decompress_frame: walk");
     check(lz4f::launch_read_finish(st, blocks, cfg.decomp_data_size, policy == hipcomp::ComputeAndVerify, cfg.get_status(),
                                    stream),
           "decompress_frame");
     check(hipGetLastError(), "decompress_frame kernels");
+  }
+
+  // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
+  // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
+  // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
+  // synchronisation of this call.  Then every frame the range touches is a ranged read of its own: range_plan.hpp
+  // over the frame's content and block_bytes, the touched blocks listed from the index, decoded (the stored ones
+  // copied), checked against their block checksums under a verifying policy, the two edge blocks through scratch
+  // slots and range_kernels.hip's slices.
+  void decompress_frame_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const hipcomp::DecompressionConfig& cfg,
+                              size_t first_byte, size_t num_bytes)
+  {
+    last_read_state = nullptr; // (until this call has a state of its own)
+    // (a configuration refused by configure_frame_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() != hipcompSuccess)
+      return;
+    if (first_byte > cfg.decomp_data_size || num_bytes > cfg.decomp_data_size - first_byte) {
+      set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
+      check(hipGetLastError(), "decompress_frame_range kernels");
+      return;
+    }
+    if (num_bytes == 0) {
+      check(hipStreamSynchronize(stream), "decompress_frame_range");
+      *cfg.get_status() = hipcompSuccess;
+      return;
+    }
+    uint8_t* s = checksum_area(ensure_scratch(frame_read_bytes(1)));
+    lz4f::ReadState* st = reinterpret_cast<lz4f::ReadState*>(s);
+    lz4f::IndexState* ix = frame_index_state(s);
+    last_read_state = st;
+    std::unique_ptr<lz4f::IndexState> hx(new lz4f::IndexState);
+    check(lz4f::launch_read_reset(st, stream), "decompress_frame_range");
+    check(lz4f::launch_index_begin(frames, frames_bytes, ix, stream), "decompress_frame_range: index");
+    check(lz4f::launch_index_list(frames, frames_bytes, ix, st, nullptr, 0, nullptr, 0, stream), "decompress_frame_range: index");
+    check(hipMemcpyAsync(hx.get(), ix, sizeof(*hx), hipMemcpyDeviceToHost, stream), "decompress_frame_range");
+    check(hipStreamSynchronize(stream), "decompress_frame_range");
+    if (!hx->ok || hx->listed != hx->blocks) {
+      *cfg.get_status() = hipcompErrorNotSupported;
+      return;
+    }
+    if (hx->content_bytes != cfg.decomp_data_size || hx->blocks != cfg.num_chunks) { // (another input's configuration)
+      *cfg.get_status() = hipcompErrorCannotDecompress;
+      return;
+    }
+    // the frames the range touches, the largest block among them, the most blocks one of them contributes
+    const uint64_t end = (uint64_t)first_byte + num_bytes;
+    uint64_t stride = 16, most = 1;
+    bool bare = false;
+    for (uint32_t k = 0; k < hx->frames; ++k) {
+      const lz4f::IndexedEntry& f = hx->frame[k];
+      if (f.out_start >= end || f.out_start + f.content_bytes <= first_byte)
+        continue;
+      const uint64_t lo = (first_byte > f.out_start ? first_byte : f.out_start) - f.out_start;
+      const uint64_t hi = (end < f.out_start + f.content_bytes ? end : f.out_start + f.content_bytes) - f.out_start;
+      const uint64_t touched = (hi - 1) / f.block_bytes - lo / f.block_bytes + 1;
+      most = touched > most ? touched : most;
+      stride = ((uint64_t)f.block_bytes + 15) / 16 * 16 > stride ? ((uint64_t)f.block_bytes + 15) / 16 * 16 : stride;
+      bare = bare || !(f.flags & lz4f::kBlockSum);
+    }
+    // scratch: the fixed part, two slots, the entry lists of a pass
+    const size_t fixed = kFrameReadFixed + 2 * (size_t)stride + 16;
+    const size_t room = scratch_bytes();
+    // (frames of blocks so much larger than this manager's chunks that its scratch space does not hold two of them:
+    // a limit of this manager, reported like the other one, kMaxIndexedFrames; the stream is idle, nothing is written)
+    if (room < fixed + lz4f::kReadEntryBytes) {
+      *cfg.get_status() = hipcompErrorNotSupported;
+      return;
+    }
+    size_t P = (room - fixed) / lz4f::kReadEntryBytes;
+    P = P < kPlacedSlab ? P : kPlacedSlab;
+    P = most < P ? (size_t)most : P;
+    s = checksum_area(ensure_scratch(fixed + lz4f::kReadEntryBytes * P));
+    st = reinterpret_cast<lz4f::ReadState*>(s);
+    last_read_state = st;
+    ix = frame_index_state(s);
+    // (the scratch may have moved: the state the kernels read is written again)
+    check(hipMemcpyAsync(ix, hx.get(), sizeof(*hx), hipMemcpyHostToDevice, stream), "decompress_frame_range");
+    check(lz4f::launch_read_reset(st, stream), "decompress_frame_range");
+    void* const ticket = s + 128;
+    RangeSlots slots;
+    slots.base = checksum_area(s + kFrameReadLists);
+    slots.stride = stride;
+    const lz4f::ReadLists l = frame_read_lists(slots.base + 2 * stride, P);
+    for (uint32_t k = 0; k < hx->frames; ++k) {
+      const lz4f::IndexedEntry& f = hx->frame[k];
+      if (f.out_start >= end || f.out_start + f.content_bytes <= first_byte)
+        continue;
+      const uint64_t lo = (first_byte > f.out_start ? first_byte : f.out_start) - f.out_start;
+      const uint64_t hi = (end < f.out_start + f.content_bytes ? end : f.out_start + f.content_bytes) - f.out_start;
+      uint8_t* const out_f = out + (f.out_start + lo - first_byte);
+      range::Plan plan;
+      if (!range::range_plan(plan, f.content_bytes, f.block_bytes, lo, hi - lo, (uint32_t)P, 2, 1, 0, 1))
+        throw std::runtime_error("decompress_frame_range: no plan"); // (lo < hi <= content_bytes: not reached)
+      for (uint64_t pass = 0; pass < plan.passes; ++pass) {
+        const uint64_t first = range::range_pass_first(plan, pass);
+        const uint32_t count = range::range_pass_count(plan, pass);
+        check(lz4f::launch_index_range_list(frames, frames_bytes, ix, k, plan, first, count, out_f, slots, l, st, stream),
+              "decompress_frame_range: block list");
+        check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, true,
+                                    stream, ticket, 64),
+              "LZ4Manager::decompress_frame_range");
+        check(lz4f::launch_read_verdict(l, st, count, stream), "decompress_frame_range: verdict");
+        check(lz4f::launch_read_stored(l, st, count, 2 * (uint64_t)f.block_bytes, stream), "decompress_frame_range: stored blocks");
+        check(lz4f::launch_index_range_settle(l, st, count, stream), "decompress_frame_range: stored blocks");
+        if (verifies())
+          check(lz4f::launch_read_block_sums(l, st, count, stream), "decompress_frame_range: block checksums");
+        // (the edge blocks are in a frame's first and last pass)
+        if (pass == 0 || pass + 1 == plan.passes)
+          check(range_launch_slices(plan, first, count, out_f, slots, l.statuses, l.actual, l.caps, stream),
+                "decompress_frame_range: slices");
+      }
+    }
+    check(lz4f::launch_index_range_finish(st, policy == hipcomp::ComputeAndVerify && bare, cfg.get_status(), stream),
+          "decompress_frame_range");
+    check(hipGetLastError(), "decompress_frame_range kernels");
   }
 
   // ---- Snappy framed streams (hipcomp/snappy.hpp; the format: snappy_frame.hpp; the kernels: snappy_frame_launch.hpp;
@@ -1166,6 +1376,21 @@ LZ4Manager::LZ4Manager(size_t uncomp_chunk_size, hipcompType_t data_type, hipStr
 }
 HCAMD_MANAGER_METHODS(LZ4Manager)
 CompressionConfig LZ4Manager::configure_frame_compression(size_t n) { return impl->core.configure_frame_compression(n); }
+CompressionConfig LZ4Manager::configure_frame_compression(size_t n, LZ4FrameIndex index)
+{
+  return impl->core.configure_frame_compression(n, index == LZ4FrameIndex::Leading);
+}
+void LZ4Manager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes,
+                                LZ4FrameIndex index)
+{
+  impl->core.compress_frame(in, frame, c, frame_bytes, index == LZ4FrameIndex::Leading);
+}
+size_t LZ4Manager::get_frame_walked_blocks() { return impl->core.frame_walked_blocks(); }
+void LZ4Manager::decompress_frame_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const DecompressionConfig& c,
+                                        size_t first_byte, size_t num_bytes)
+{
+  impl->core.decompress_frame_range(out, frames, frames_bytes, c, first_byte, num_bytes);
+}
 void LZ4Manager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
 {
   impl->core.compress_frame(in, frame, c, frame_bytes);

@@ -201,10 +201,11 @@ __global__ void read_reset_kernel(ReadState* st)
 // the entry of a frame's last block says so (kLast) and its trailer is behind the walk.
 // lists: false counts only and goes to the end.  final: the caller expects no more blocks; one that comes stops the
 // walk short of the end.
-__global__ void read_walk_kernel(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists, uint32_t capacity,
-                                 bool final, bool verify)
+__device__ __forceinline__ void read_walk(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists,
+                                          uint32_t capacity, bool final, bool verify)
 {
   ReadState st = *stp;
+  const uint64_t blocks_before = st.blocks;
   uint32_t count = 0;
   int32_t head = -1;
   while (st.reason == kOk && !st.done) {
@@ -334,7 +335,25 @@ __global__ void read_walk_kernel(const uint8_t* in, uint64_t n, ReadState* stp, 
       l.aux[i] = kNoContentSize;
     }
   }
+  st.walked += (uint32_t)(st.blocks - blocks_before); // (the blocks this call stepped over)
   *stp = st;
+}
+
+__global__ void read_walk_kernel(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists, uint32_t capacity,
+                                 bool final, bool verify)
+{
+  read_walk(in, n, stp, l, lists, capacity, final, verify);
+}
+
+// The walk behind the passes of an indexed read (lz4_frame_index_launch.hpp): where they listed and placed everything,
+// *skip says so and nothing is left to do here.  (A kernel of its own: the walk of a frame without an index is the
+// kernel above, without a word to load and test.)
+__global__ void read_walk_unless_kernel(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists,
+                                        uint32_t capacity, bool final, bool verify, const uint32_t* skip)
+{
+  if (*skip)
+    return;
+  read_walk(in, n, stp, l, lists, capacity, final, verify);
 }
 
 // ---- reading: sizes and places -------------------------------------------------------------------------------
@@ -695,10 +714,14 @@ hipError_t launch_read_reset(ReadState* st, hipStream_t stream)
 }
 
 hipError_t launch_read_walk(const uint8_t* in, uint64_t in_bytes, ReadState* st, const ReadLists* lists, uint32_t capacity,
-                            bool verify, hipStream_t stream)
+                            bool verify, hipStream_t stream, const uint32_t* skip)
 {
-  read_walk_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity,
-                                        lists != nullptr && capacity == 0, verify);
+  if (skip)
+    read_walk_unless_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity,
+                                                 lists != nullptr && capacity == 0, verify, skip);
+  else
+    read_walk_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity,
+                                          lists != nullptr && capacity == 0, verify);
   return hipGetLastError();
 }
 

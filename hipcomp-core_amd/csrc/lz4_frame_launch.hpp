@@ -63,6 +63,7 @@ struct ReadState
   uint32_t done;            // the walk stands at the end of the input
   uint32_t count;           // entries of this pass
   uint32_t verdict;         // kVerdict* bits
+  uint32_t walked;          // data blocks the walk itself stepped over since the reset: every call of it adds its own, nothing else does
 };
 
 // The entries of a pass, one per data block (device memory, the manager's scratch).
@@ -85,9 +86,10 @@ constexpr size_t kReadEntryBytes = 9 * 8 + 3 * 4;
 
 hipError_t launch_read_reset(ReadState* st, hipStream_t stream);
 // Follows the chain from where the last pass stopped, for up to `capacity` blocks; lists == nullptr: to the end of
-// the input, counting only.  verify: an empty frame's content checksum is compared here.
+// the input, counting only.  verify: an empty frame's content checksum is compared here.  skip: a device word that
+// says the indexed read (lz4_frame_index_launch.hpp) has done it all -- the walk (a kernel of its own then) returns at once.
 hipError_t launch_read_walk(const uint8_t* in, uint64_t in_bytes, ReadState* st, const ReadLists* lists, uint32_t capacity,
-                            bool verify, hipStream_t stream);
+                            bool verify, hipStream_t stream, const uint32_t* skip = nullptr);
 // sizes[] of the compressed blocks of linked frames (the batched decoder's parse-only pass gives the others' in actual[])
 hipError_t launch_read_linked_sizes(const ReadLists& l, const ReadState* st, uint32_t capacity, hipStream_t stream);
 // sizes[], out_ptrs[], caps[], batch_caps[] from a scan that continues from st->out_cursor; checks block maxima,

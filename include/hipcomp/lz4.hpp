@@ -16,6 +16,13 @@ struct LZ4FormatSpecHeader
   hipcompType_t data_type;
 };
 
+/* where compress_frame puts the block index of a seekable frame: nowhere, or in front of the frame */
+enum class LZ4FrameIndex
+{
+  None,
+  Leading
+};
+
 struct LZ4Manager : hipcompManagerBase
 {
   /* uncomp_chunk_size at most 16 MiB (the LZ4 block limit); device_id must be the current device */
@@ -74,6 +81,39 @@ struct LZ4Manager : hipcompManagerBase
   DecompressionConfig configure_frame_decompression(const uint8_t* frames, size_t frames_bytes);
   void decompress_frame(uint8_t* decomp_buffer, const uint8_t* frames, size_t frames_bytes,
                         const DecompressionConfig& decomp_config);
+
+  /* ---- Seekable LZ4 frames: a block index in a skippable frame in front of the frame it describes ----
+     INTEGRATION.md, "Seekable LZ4 frames", has the layout, the contract and the fallback rule.
+     Writing: LZ4FrameIndex::None is the call above, byte for byte.  Leading writes the index -- magic 0x184D2A54,
+     "HCLZ4IDX", version, flags, uncomp_chunk_size, the number of blocks, the content size, the size word of every
+     block as it stands in the frame, an XXH32: 44 + 4 * num_chunks bytes -- and behind it the very frame the call
+     above writes for the same input.  Every reader of the format skips the index, the result is still a plain
+     .lz4 file.  max_compressed_buffer_size is the bound above plus 44 + 4 * num_chunks, *frame_bytes counts the
+     index, the call stays asynchronous and get_required_scratch_buffer_size() what it is.
+     Reading: configure_frame_decompression and decompress_frame find the index themselves.  Where `frames` is
+     indexed frames of the form written here and nothing else but skippable frames of other magics between them,
+     the blocks are found by a scan of the index and not by following the chain of size words, and no block is
+     parsed twice.  The index is untrusted: it is used only where every word of it is found in its place in the
+     frame and every compressed block decodes to exactly its share of the content; in every other case the call
+     carries on as if the index were any skippable frame, with the status, size and bytes it has without it. */
+  CompressionConfig configure_frame_compression(size_t decomp_buffer_size, LZ4FrameIndex index);
+  void compress_frame(const uint8_t* decomp_buffer, uint8_t* frame, const CompressionConfig& comp_config,
+                      size_t* frame_bytes, LZ4FrameIndex index);
+  /* Bytes [first_byte, first_byte + num_bytes) of the content decompress_frame would produce for `frames` into
+     out[0, num_bytes): only the blocks the range touches are read, decoded (stored ones copied) and, under a
+     verifying policy, checked against their block checksums.  `frames` has to be indexed frames as written with
+     LZ4FrameIndex::Leading -- several of them, skippable frames of other magics between them -- and every index
+     has to be found in its frame, size word for size word: anything else is hipcompErrorNotSupported with nothing
+     written to out.  A range that ends beyond decomp_config.decomp_data_size is hipcompErrorInvalidValue;
+     num_bytes == 0 succeeds and launches nothing.  A touched block that does not decode to its share of the
+     content is hipcompErrorCannotDecompress, a wrong block checksum hipcompErrorBadChecksum; blocks the range
+     does not touch are not looked at.  Reads stay inside frames[0, frames_bytes), writes inside out[0, num_bytes)
+     and the scratch.  The call synchronises the stream once: the host reads the table of frames the device made. */
+  void decompress_frame_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes,
+                              const DecompressionConfig& decomp_config, size_t first_byte, size_t num_bytes);
+  /* the data blocks the last decompress_frame found by following the chain: 0 where the index served, num_chunks
+     where it did not.  Synchronises the stream; meant for tests and for telling why a read was slow. */
+  size_t get_frame_walked_blocks();
 
 private:
   struct Impl;

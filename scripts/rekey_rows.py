@@ -1,12 +1,17 @@
-"""rekey_rows.py OUT.json --added NAME [NAME ...]: carry the newest profiles/rNN_rows.json over to a build that only
-ADDED kernel objects (csrc/NAME.hip), without measuring again.
+"""rekey_rows.py OUT.json --added NAME [NAME ...] [--changed NAME [NAME ...] --parent-asm DIR]: carry the newest
+profiles/rNN_rows.json over to a build that only ADDED kernel objects (csrc/NAME.hip), or changed objects that hold
+none of the measured kernels, without measuring again.
 
 bench.py attaches the committed rocprof rows to its result only on the build they were measured on (the ids of
 bench.kernel_source_id / bench.device_asm_id).  A new kernel file changes both ids although no measured kernel
 changed.  This script proves that from the build at hand (csrc/build/*.gfx950.s, which build() leaves there): the
 device assembly of every object but the added ones must hash to the table's device_asm_sha16 -- the measured kernels
 are the same code, instruction for instruction -- and only then writes the same rows under the new ids, saying so
-in the table's "_how".  Anything else (a changed kernel) is refused: collect again (scripts/collect_profiles.sh)."""
+in the table's "_how".  --changed NAME: the object's assembly differs from the table's build, and that is
+allowed only where no kernel the rows name is defined in it (neither in this build's assembly of it nor in the
+parent's); the parent build's assembly of it is read from DIR (its build/*.gfx950.s) so that the table's id can
+still be reproduced from all objects but the added ones.  Anything else (a changed measured kernel) is refused:
+collect again (scripts/collect_profiles.sh)."""
 import argparse
 import glob
 import hashlib
@@ -22,7 +27,10 @@ import bench  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("out")
 ap.add_argument("--added", nargs="+", required=True)
+ap.add_argument("--changed", nargs="*", default=[])
+ap.add_argument("--parent-asm")
 a = ap.parse_args()
+assert not a.changed or a.parent_asm, "--changed needs --parent-asm DIR"
 
 tables = sorted(glob.glob(os.path.join(ROOT, "profiles", "r??_rows.json")), reverse=True)
 tables = [t for t in tables if os.path.abspath(t) != os.path.abspath(a.out)]
@@ -35,19 +43,30 @@ for path in files:                       # (bench.device_asm_id over the objects
     if os.path.basename(path).split(".")[0] in a.added:
         continue
     h.update(os.path.basename(path).encode())
-    with open(path, "rb") as f:
-        h.update(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", f.read()))
+    name = os.path.basename(path).split(".")[0]
+    with open(os.path.join(a.parent_asm, os.path.basename(path)) if name in a.changed else path, "rb") as f:
+        text = f.read()
+    h.update(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", text))
+    if name in a.changed:   # none of the measured kernels lives here, before or after
+        measured = {phase["kernel"].split("<")[0] for row in old["rows"].values() for phase in row.values()
+                    if isinstance(phase, dict) and "kernel" in phase}
+        with open(path, "rb") as f:
+            both = text + f.read()
+        hit = sorted(k for k in measured if re.search(rb"\b%s\b" % re.escape(k.encode()), both))
+        assert not hit, "csrc/%s.hip defines measured kernels %s: collect again" % (name, hit)
 same = h.hexdigest()[:16]
 if same != old.get("device_asm_sha16"):
     sys.exit("%s was measured on assembly %s; the build at hand without %s has %s: a measured kernel changed, collect again"
              % (tables[0], old.get("device_asm_sha16"), a.added, same))
 new = dict(old)
 new["_how"] = old["_how"] + (
-    "\nCarried over by scripts/rekey_rows.py from %s (sources %s, assembly %s): this build only added %s, and the "
+    "\nCarried over by scripts/rekey_rows.py from %s (sources %s, assembly %s): this build only added %s%s, and the "
     "device assembly of every other kernel object is that table's, instruction for instruction (checked from "
     "csrc/build/*.gfx950.s); nothing was measured again." % (
         os.path.basename(tables[0]), old.get("kernel_source_sha16"), old.get("device_asm_sha16"),
-        ", ".join("csrc/%s.hip" % n for n in a.added)))
+        ", ".join("csrc/%s.hip" % n for n in a.added),
+        " and changed %s, which holds none of the measured kernels (checked against the parent build's assembly of it)"
+        % ", ".join("csrc/%s.hip" % n for n in a.changed) if a.changed else ""))
 new["kernel_source_sha16"] = bench.kernel_source_id()
 new["device_asm_sha16"] = bench.device_asm_id()
 with open(a.out, "w") as f:
