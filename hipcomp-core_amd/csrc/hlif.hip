@@ -22,6 +22,7 @@
 #include "lz4_frame_launch.hpp"
 #include "lz4_launch.hpp"
 #include "range_launch.hpp"
+#include "snappy_frame_index_launch.hpp"
 #include "snappy_frame_launch.hpp"
 #include "snappy_launch.hpp"
 #include "wave_utils.hpp"
@@ -1143,8 +1144,13 @@ struct Core
     }
     return lo;
   }
-  // Reading, a pass of P chunks: the walk's state (128 bytes), the entry lists.
-  static constexpr size_t kSzReadFixed = 16 + 128;
+  // Reading, a pass of P chunks: the walk's state (128 bytes), the indexed read's state
+  // (snappy_frame_index_launch.hpp), the entry lists.  The required scratch is what it was, so a pass of every
+  // framed read, indexed or not, holds 1664 / kReadEntryBytes = 30 entries fewer than before the index.
+  static constexpr size_t kSzReadLists = 1792;
+  static constexpr size_t kSzReadFixed = 16 + kSzReadLists;
+  static_assert(128 + sizeof(szf::IndexState) <= kSzReadLists, "the indexed read's state does not fit");
+  static szf::IndexState* sz_index_state(uint8_t* s) { return reinterpret_cast<szf::IndexState*>(s + 128); }
   size_t sz_read_bytes(size_t P) const { return kSzReadFixed + szf::kReadEntryBytes * P; }
   size_t sz_read_pass(size_t chunks) const
   {
@@ -1167,23 +1173,32 @@ struct Core
     return l;
   }
 
-  hipcomp::CompressionConfig sz_configure_compression(size_t decomp_buffer_size) const
+  // index: the stream gets its chunk index behind the identifier (snappy_frame_index.hpp), 40 + 4 * num_chunks
+  // bytes more
+  hipcomp::CompressionConfig sz_configure_compression(size_t decomp_buffer_size, bool index = false) const
   {
     hipcomp::CompressionConfig c(decomp_buffer_size);
-    if (chunk_bytes > szf::kMaxContent) { // no data chunk of the format holds a chunk
+    // no data chunk of the format holds a chunk; the index's length field does not hold the words
+    if (chunk_bytes > szf::kMaxContent
+        || (index && (decomp_buffer_size + chunk_bytes - 1) / chunk_bytes > szf::kIndexMaxChunks)) {
       *c.get_status() = hipcompErrorInvalidValue;
       return c;
     }
     c.num_chunks = (decomp_buffer_size + chunk_bytes - 1) / chunk_bytes;
-    c.max_compressed_buffer_size = (size_t)szf::frame_bound(c.num_chunks, chunk_bytes);
+    c.max_compressed_buffer_size =
+        (size_t)(index ? szf::indexed_frame_bound(c.num_chunks, chunk_bytes) : szf::frame_bound(c.num_chunks, chunk_bytes));
     return c;
   }
 
-  void sz_compress(const uint8_t* decomp_buffer, uint8_t* frame, const hipcomp::CompressionConfig& cfg, size_t* frame_bytes)
+  // index: the room of the index is left behind the identifier, its words are written pass by pass from the lists
+  // the chunks are written from, its CRC when they all stand
+  void sz_compress(const uint8_t* decomp_buffer, uint8_t* frame, const hipcomp::CompressionConfig& cfg, size_t* frame_bytes,
+                   bool index = false)
   {
     if (reinterpret_cast<uintptr_t>(frame_bytes) & 7)
       throw std::runtime_error("compress_frame: frame_bytes must be 8-byte aligned");
-    if (chunk_bytes > szf::kMaxContent) {
+    if (chunk_bytes > szf::kMaxContent
+        || (index && (cfg.uncompressed_buffer_size + chunk_bytes - 1) / chunk_bytes > szf::kIndexMaxChunks)) {
       set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
       check(szf::launch_set_size(frame_bytes, 0, stream), "compress_frame");
       return;
@@ -1202,7 +1217,12 @@ struct Core
     l.crcs = reinterpret_cast<uint32_t*>(lists + 40 * P);
     uint8_t* const slots = checksum_area(lists + szf::kWriteEntryBytes * P);
     set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompSuccess);
-    check(szf::launch_write_begin(frame, cursor, stream), "compress_frame: identifier");
+    uint8_t* const index_at = frame + szf::kIdentifierBytes;
+    if (index)
+      check(szf::launch_index_write_begin(frame, cursor, (uint32_t)n, (uint32_t)chunk_bytes, cfg.uncompressed_buffer_size, stream),
+            "compress_frame: index");
+    else
+      check(szf::launch_write_begin(frame, cursor, stream), "compress_frame: identifier");
     for (size_t first = 0; first < n; first += P) {
       const uint32_t count = (uint32_t)(n - first < P ? n - first : P);
       check(szf::launch_write_lists(decomp_buffer, cfg.uncompressed_buffer_size, chunk_bytes, first, count, slots, slot_bytes,
@@ -1214,16 +1234,60 @@ struct Core
       check(szf::launch_write_crcs(l, count, stream), "compress_frame: checksums");
       check(szf::launch_write_scan(l, count, cursor, stream), "compress_frame: scan");
       check(szf::launch_write_chunks(frame, l, count, chunk_bytes, stream), "compress_frame: chunks");
+      if (index)
+        check(szf::launch_index_write_words(index_at, l, first, count, stream), "compress_frame: index");
     }
+    if (index)
+      check(szf::launch_index_write_end(index_at, (uint32_t)n, stream), "compress_frame: index");
     check(szf::launch_write_end(cursor, frame_bytes, stream), "compress_frame: length");
     check(hipGetLastError(), "compress_frame kernels");
+  }
+
+  // What configure_frame_decompression found in the buffer it saw last: decompress_frame does not launch the
+  // indexed passes for a buffer that had no index then.  A hint and no more -- the passes themselves decide on the
+  // device, whatever the buffer holds by now.
+  const uint8_t* sz_hint_frames = nullptr;
+  size_t sz_hint_bytes = 0;
+  bool sz_hint_indexed = false;
+  // the state of the last decompress_frame or decompress_frame_range
+  szf::ReadState* sz_last_read_state = nullptr;
+
+  // Data chunks the chain's walk stepped over in the last decompress_frame or decompress_frame_range (synchronises
+  // the stream): ReadState::walked, which the walk alone adds to.
+  size_t sz_walked_chunks()
+  {
+    if (!sz_last_read_state)
+      return 0;
+    szf::ReadState h;
+    check(hipMemcpyAsync(&h, sz_last_read_state, sizeof(h), hipMemcpyDeviceToHost, stream), "get_frame_walked_chunks");
+    check(hipStreamSynchronize(stream), "get_frame_walked_chunks");
+    return (size_t)h.walked;
   }
 
   hipcomp::DecompressionConfig sz_configure_decompression(const uint8_t* frames, size_t frames_bytes)
   {
     hipcomp::DecompressionConfig d;
-    szf::ReadState* const st = reinterpret_cast<szf::ReadState*>(checksum_area(ensure_scratch(sz_read_bytes(1))));
+    uint8_t* const s = checksum_area(ensure_scratch(sz_read_bytes(1)));
+    szf::ReadState* const st = reinterpret_cast<szf::ReadState*>(s);
     szf::ReadState h;
+    // indexed units and nothing else: the numbers are the indexes', every chunk tested in its place
+    {
+      szf::IndexState* const ix = sz_index_state(s);
+      szf::IndexState hx;
+      check(szf::launch_index_begin(frames, frames_bytes, ix, stream), "configure_frame_decompression: index");
+      check(szf::launch_index_list(frames, frames_bytes, ix, st, nullptr, 0, stream), "configure_frame_decompression: index");
+      check(hipMemcpyAsync(&hx, ix, offsetof(szf::IndexState, unit), hipMemcpyDeviceToHost, stream),
+            "configure_frame_decompression");
+      check(hipStreamSynchronize(stream), "configure_frame_decompression");
+      sz_hint_frames = frames;
+      sz_hint_bytes = frames_bytes;
+      sz_hint_indexed = hx.ok && hx.listed == hx.chunks;
+      if (sz_hint_indexed) {
+        d.num_chunks = (uint32_t)hx.chunks;
+        d.decomp_data_size = (size_t)hx.content_bytes;
+        return d;
+      }
+    }
     check(szf::launch_read_reset(st, stream), "configure_frame_decompression");
     check(szf::launch_read_walk(frames, frames_bytes, st, nullptr, 0, stream), "configure_frame_decompression");
     check(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, stream), "configure_frame_decompression");
@@ -1245,13 +1309,39 @@ struct Core
     const size_t chunks = cfg.num_chunks, P = sz_read_pass(chunks);
     uint8_t* const s = checksum_area(ensure_scratch(sz_read_bytes(P)));
     szf::ReadState* const st = reinterpret_cast<szf::ReadState*>(s);
-    const szf::ReadLists l = sz_read_lists(s + 128, P);
+    // (no indexed passes for a buffer that had no index when it was configured: the launches of a manager without
+    // the index, one for one)
+    const bool try_index = !(sz_hint_frames == frames && sz_hint_bytes == frames_bytes && !sz_hint_indexed);
+    szf::IndexState* const ix = try_index ? sz_index_state(s) : nullptr;
+    sz_last_read_state = st;
+    const szf::ReadLists l = sz_read_lists(s + kSzReadLists, P);
     check(szf::launch_read_reset(st, stream), "decompress_frame");
+    // The indexed passes: entries from the index (no walk), the placing scan, the batched decoder, the stored chunks,
+    // the CRCs.  Whether they held is a word on the device: if so the chain's passes below find nothing to do, if
+    // not they start from the reset state and do it all.
+    if (try_index) {
+      check(szf::launch_index_begin(frames, frames_bytes, ix, stream), "decompress_frame: index");
+      for (size_t first = 0; first < chunks; first += P) {
+        const uint32_t count = (uint32_t)(chunks - first < P ? chunks - first : P);
+        check(szf::launch_index_list(frames, frames_bytes, ix, st, &l, count, stream), "decompress_frame: index");
+        check(szf::launch_read_scan(l, st, decomp_buffer, cfg.decomp_data_size, stream), "decompress_frame: scan");
+        snappy_launch_decompress(l.payloads, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, stream);
+        check(hipGetLastError(), "SnappyManager::decompress_frame");
+        check(szf::launch_index_verdict(l, st, ix, count, stream), "decompress_frame: index");
+        check(szf::launch_read_stored(l, st, count, 2 * (uint64_t)(cfg.decomp_data_size / chunks), stream),
+              "decompress_frame: stored chunks");
+        if (verifies())
+          check(szf::launch_read_crcs(l, st, count, stream), "decompress_frame: checksums");
+      }
+      check(szf::launch_index_end(ix, st, l, (uint32_t)(chunks < P ? chunks : P), frames, frames_bytes, chunks, stream),
+            "decompress_frame: index");
+    }
+    const uint32_t* const skip = ix ? &ix->skip : nullptr;
     if (chunks == 0) // identifiers and padding at the most
-      check(szf::launch_read_walk(frames, frames_bytes, st, &l, 0, stream), "decompress_frame: walk");
+      check(szf::launch_read_walk(frames, frames_bytes, st, &l, 0, stream, skip), "decompress_frame: walk");
     for (size_t first = 0; first < chunks; first += P) {
       const uint32_t count = (uint32_t)(chunks - first < P ? chunks - first : P);
-      check(szf::launch_read_walk(frames, frames_bytes, st, &l, count, stream), "decompress_frame: walk");
+      check(szf::launch_read_walk(frames, frames_bytes, st, &l, count, stream, skip), "decompress_frame: walk");
       check(szf::launch_read_scan(l, st, decomp_buffer, cfg.decomp_data_size, stream), "decompress_frame: scan");
       snappy_launch_decompress(l.payloads, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, stream);
       check(hipGetLastError(), "SnappyManager::decompress_frame");
@@ -1264,6 +1354,118 @@ struct Core
     }
     check(szf::launch_read_finish(st, chunks, cfg.decomp_data_size, cfg.get_status(), stream), "decompress_frame");
     check(hipGetLastError(), "decompress_frame kernels");
+  }
+
+  // ---- a ranged read of seekable streams: bytes [first_byte, first_byte + num_bytes) of the content into out ----
+  // The whole input has to be indexed units: the hop and the test of every chunk in its place (of no chunk more is
+  // read for it than its first 16 bytes) say so on the device, and the host reads the unit table they leave -- the
+  // one synchronisation of this call.  Then every unit the range touches is a ranged read of its own: range_plan.hpp
+  // over the unit's content and chunk_bytes, the touched chunks listed from the index, decoded (the stored ones
+  // copied), checked against their CRCs under a verifying policy, the two edge chunks through scratch slots and
+  // range_kernels.hip's slices.
+  void sz_decompress_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const hipcomp::DecompressionConfig& cfg,
+                           size_t first_byte, size_t num_bytes)
+  {
+    sz_last_read_state = nullptr; // (until this call has a state of its own)
+    // (a configuration refused by configure_frame_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() != hipcompSuccess)
+      return;
+    if (first_byte > cfg.decomp_data_size || num_bytes > cfg.decomp_data_size - first_byte) {
+      set_status_kernel<<<1, 1, 0, stream>>>(cfg.get_status(), hipcompErrorInvalidValue);
+      check(hipGetLastError(), "decompress_frame_range kernels");
+      return;
+    }
+    if (num_bytes == 0) {
+      check(hipStreamSynchronize(stream), "decompress_frame_range");
+      *cfg.get_status() = hipcompSuccess;
+      return;
+    }
+    uint8_t* s = checksum_area(ensure_scratch(sz_read_bytes(1)));
+    szf::ReadState* st = reinterpret_cast<szf::ReadState*>(s);
+    szf::IndexState* ix = sz_index_state(s);
+    sz_last_read_state = st;
+    std::unique_ptr<szf::IndexState> hx(new szf::IndexState);
+    check(szf::launch_read_reset(st, stream), "decompress_frame_range");
+    check(szf::launch_index_begin(frames, frames_bytes, ix, stream), "decompress_frame_range: index");
+    check(szf::launch_index_list(frames, frames_bytes, ix, st, nullptr, 0, stream), "decompress_frame_range: index");
+    check(hipMemcpyAsync(hx.get(), ix, sizeof(*hx), hipMemcpyDeviceToHost, stream), "decompress_frame_range");
+    check(hipStreamSynchronize(stream), "decompress_frame_range");
+    if (!hx->ok || hx->listed != hx->chunks) {
+      *cfg.get_status() = hipcompErrorNotSupported;
+      return;
+    }
+    if (hx->content_bytes != cfg.decomp_data_size || hx->chunks != cfg.num_chunks) { // (another input's configuration)
+      *cfg.get_status() = hipcompErrorCannotDecompress;
+      return;
+    }
+    // the units the range touches, the largest chunk among them, the most chunks one of them contributes
+    const uint64_t end = (uint64_t)first_byte + num_bytes;
+    uint64_t stride = 16, most = 1;
+    for (uint32_t k = 0; k < hx->units; ++k) {
+      const szf::IndexedEntry& f = hx->unit[k];
+      if (f.out_start >= end || f.out_start + f.content_bytes <= first_byte)
+        continue;
+      const uint64_t lo = (first_byte > f.out_start ? first_byte : f.out_start) - f.out_start;
+      const uint64_t hi = (end < f.out_start + f.content_bytes ? end : f.out_start + f.content_bytes) - f.out_start;
+      const uint64_t touched = (hi - 1) / f.chunk_bytes - lo / f.chunk_bytes + 1;
+      most = touched > most ? touched : most;
+      stride = ((uint64_t)f.chunk_bytes + 15) / 16 * 16 > stride ? ((uint64_t)f.chunk_bytes + 15) / 16 * 16 : stride;
+    }
+    // scratch: the fixed part, two slots, the entry lists of a pass with a size_t more per entry (the shares, for
+    // the slices)
+    const size_t fixed = kSzReadFixed + 2 * (size_t)stride + 16, entry = szf::kReadEntryBytes + 8;
+    const size_t room = scratch_bytes();
+    // (units of chunks so much larger than this manager's that its scratch space does not hold two of them: a limit
+    // of this manager, reported like the other one, kMaxIndexedStreams; the stream is idle, nothing is written)
+    if (room < fixed + entry) {
+      *cfg.get_status() = hipcompErrorNotSupported;
+      return;
+    }
+    size_t P = (room - fixed) / entry;
+    P = P < kPlacedSlab ? P : kPlacedSlab;
+    P = most < P ? (size_t)most : P;
+    s = checksum_area(ensure_scratch(fixed + entry * P));
+    st = reinterpret_cast<szf::ReadState*>(s);
+    sz_last_read_state = st;
+    ix = sz_index_state(s);
+    // (the scratch may have moved: the state the kernels read is written again)
+    check(hipMemcpyAsync(ix, hx.get(), sizeof(*hx), hipMemcpyHostToDevice, stream), "decompress_frame_range");
+    check(szf::launch_read_reset(st, stream), "decompress_frame_range");
+    RangeSlots slots;
+    slots.base = checksum_area(s + kSzReadLists);
+    slots.stride = stride;
+    size_t* const caps = reinterpret_cast<size_t*>(slots.base + 2 * stride);
+    const szf::ReadLists l = sz_read_lists(slots.base + 2 * stride + 8 * P, P);
+    for (uint32_t k = 0; k < hx->units; ++k) {
+      const szf::IndexedEntry& f = hx->unit[k];
+      if (f.out_start >= end || f.out_start + f.content_bytes <= first_byte)
+        continue;
+      const uint64_t lo = (first_byte > f.out_start ? first_byte : f.out_start) - f.out_start;
+      const uint64_t hi = (end < f.out_start + f.content_bytes ? end : f.out_start + f.content_bytes) - f.out_start;
+      uint8_t* const out_f = out + (f.out_start + lo - first_byte);
+      range::Plan plan;
+      if (!range::range_plan(plan, f.content_bytes, f.chunk_bytes, lo, hi - lo, (uint32_t)P, 2, 1, 0, 1))
+        throw std::runtime_error("decompress_frame_range: no plan"); // (lo < hi <= content_bytes: not reached)
+      for (uint64_t pass = 0; pass < plan.passes; ++pass) {
+        const uint64_t first = range::range_pass_first(plan, pass);
+        const uint32_t count = range::range_pass_count(plan, pass);
+        check(szf::launch_index_range_list(frames, frames_bytes, ix, k, plan, first, count, out_f, slots, l, caps, st, stream),
+              "decompress_frame_range: chunk list");
+        snappy_launch_decompress(l.payloads, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, stream);
+        check(hipGetLastError(), "SnappyManager::decompress_frame_range");
+        check(szf::launch_read_verdict(l, st, count, stream), "decompress_frame_range: verdict");
+        check(szf::launch_read_stored(l, st, count, 2 * (uint64_t)f.chunk_bytes, stream), "decompress_frame_range: stored chunks");
+        check(szf::launch_index_range_settle(l, caps, st, count, stream), "decompress_frame_range: stored chunks");
+        if (verifies())
+          check(szf::launch_read_crcs(l, st, count, stream), "decompress_frame_range: checksums");
+        // (the edge chunks are in a unit's first and last pass)
+        if (pass == 0 || pass + 1 == plan.passes)
+          check(range_launch_slices(plan, first, count, out_f, slots, l.statuses, l.actual, caps, stream),
+                "decompress_frame_range: slices");
+      }
+    }
+    check(szf::launch_index_range_finish(st, cfg.get_status(), stream), "decompress_frame_range");
+    check(hipGetLastError(), "decompress_frame_range kernels");
   }
 
   void set_scratch_buffer(uint8_t* new_scratch_buffer)
@@ -1424,6 +1626,21 @@ SnappyManager::SnappyManager(size_t uncomp_chunk_size, hipStream_t user_stream, 
 }
 HCAMD_MANAGER_METHODS(SnappyManager)
 CompressionConfig SnappyManager::configure_frame_compression(size_t n) { return impl->core.sz_configure_compression(n); }
+CompressionConfig SnappyManager::configure_frame_compression(size_t n, SnappyFrameIndex index)
+{
+  return impl->core.sz_configure_compression(n, index == SnappyFrameIndex::Leading);
+}
+void SnappyManager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes,
+                                   SnappyFrameIndex index)
+{
+  impl->core.sz_compress(in, frame, c, frame_bytes, index == SnappyFrameIndex::Leading);
+}
+size_t SnappyManager::get_frame_walked_chunks() { return impl->core.sz_walked_chunks(); }
+void SnappyManager::decompress_frame_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes, const DecompressionConfig& c,
+                                           size_t first_byte, size_t num_bytes)
+{
+  impl->core.sz_decompress_range(out, frames, frames_bytes, c, first_byte, num_bytes);
+}
 void SnappyManager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
 {
   impl->core.sz_compress(in, frame, c, frame_bytes);

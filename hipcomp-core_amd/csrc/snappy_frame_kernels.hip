@@ -8,22 +8,14 @@
 // lists the data chunks of a pass with what their first 13 bytes say: payload, kind, stored CRC, output bytes.
 // Places come from a scan; the batched decoder takes the compressed chunks, a copy the stored ones, and the CRC
 // kernel compares.  Every store is a vector store.
-#include "crc32c_math.hpp"
 #include "device_facts.hpp"
+#include "snappy_frame_device.hiph"
 #include "snappy_frame_launch.hpp"
-#include "wave_utils.hpp"
 
 namespace hcamd {
 namespace szf {
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kScanBlock = 1024;
-constexpr int kWavesPerBlock = kBlock / kWave;
-
-__device__ const crc32c::Tables kCrcTables = crc32c::make_tables();
-__device__ const crc32c::ShiftTable kCrcShift = crc32c::make_shift_table();
 
 // ---- shared pieces -------------------------------------------------------------------------------------------
 // n bytes dst <- src by `threads` threads, this one number t: 16-byte aligned stores, 16-byte loads wherever they
@@ -55,105 +47,6 @@ __device__ __forceinline__ void strided_copy(gptr dst, cgptr src, uint64_t n, ui
   const uint64_t tail = n & 15u;
   if (t < tail)
     dst[(nvec << 4) + t] = src[(nvec << 4) + t];
-}
-
-// exclusive scan over the kScanBlock threads of a workgroup; total: the sum
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* lds, uint64_t& total)
-{
-  const uint64_t incl = wave_scan_add_u64(v);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63)
-    lds[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t run = 0;
-    for (int w = 0; w < kScanBlock / kWave; ++w) {
-      const uint64_t t = lds[w];
-      lds[w] = run;
-      run += t;
-    }
-    lds[kScanBlock / kWave] = run;
-  }
-  __syncthreads();
-  const uint64_t excl = incl - v + lds[wave];
-  total = lds[kScanBlock / kWave];
-  __syncthreads();
-  return excl;
-}
-
-// ---- CRC-32C: checksum_kernels.hip's chunk kernel over the Castagnoli polynomial ------------------------------
-struct LdsTables
-{
-  crc32c::Tables s;
-  uint32_t x2n[crc32c::kShiftBits];
-};
-
-__device__ __forceinline__ void fill_tables(LdsTables& L)
-{
-  const u32x4* src = reinterpret_cast<const u32x4*>(&kCrcTables);
-  u32x4* dst = reinterpret_cast<u32x4*>(&L.s);
-  for (uint32_t k = threadIdx.x; k < sizeof(crc32c::Tables) / 16; k += blockDim.x)
-    dst[k] = src[k];
-  if (threadIdx.x < crc32c::kShiftBits)
-    L.x2n[threadIdx.x] = kCrcShift.x2n[threadIdx.x];
-  __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-  for (int d = 1; d < kWave; d <<= 1)
-    v ^= (uint32_t)__shfl_xor((int)v, d, kWave);
-  return v;
-}
-
-// The CRC-32C of p[0, n), n <= 65536, by all 64 lanes of the wave, the result in every lane.  The 16-byte aligned
-// middle is cut into 64 contiguous per-lane segments of whole 16-byte blocks; lane 0 also takes the bytes in front
-// of the first aligned block, the lane with the last block the bytes behind it; the segments' CRCs are joined by
-// crc32c_shift.  No byte outside p[0, n) is read.  No byte at all: the CRC of nothing, 0.
-__device__ __forceinline__ uint32_t wave_crc(const LdsTables& L, const uint8_t* p, uint32_t n, int lane)
-{
-  const uintptr_t start = reinterpret_cast<uintptr_t>(p), end = start + n;
-  const uintptr_t a = (start + 15) & ~uintptr_t(15), b = end & ~uintptr_t(15);
-  const uint32_t nblk = b > a ? (uint32_t)((b - a) / 16) : 0;
-  uint32_t s = 0, e = 0;           // this lane's 16-byte blocks [s, e) from a
-  uint32_t head_n = 0, tail_n = 0; // bytes in front of the blocks (lane 0) and behind them (the lane with the last block)
-  uint32_t seg_end = 0;            // where this lane's segment ends (bytes from p)
-  if (nblk == 0) {
-    if (lane == 0) {
-      head_n = n;
-      seg_end = n;
-    }
-  } else {
-    const uint32_t per = (nblk + kWave - 1) / kWave;
-    s = (uint32_t)lane * per;
-    e = s + per;
-    s = s < nblk ? s : nblk;
-    e = e < nblk ? e : nblk;
-    if (lane == 0)
-      head_n = (uint32_t)(a - start);
-    if (e == nblk && s < e)
-      tail_n = (uint32_t)(end - b);
-    seg_end = (uint32_t)(a - start) + e * 16 + tail_n;
-  }
-  uint32_t reg = 0xFFFFFFFFu;
-  reg = crc32c::crc32c_update_bytes(L.s.t[0], reg, p, head_n);
-  const HC_GLOBAL u32x4* q = reinterpret_cast<const HC_GLOBAL u32x4*>(a);
-  uint32_t j = s;
-  for (; j + 4 <= e; j += 4) {
-    const u32x4 v0 = q[j], v1 = q[j + 1], v2 = q[j + 2], v3 = q[j + 3];
-    reg = crc32c::crc32c_update_16(L.s, reg, v0.x, v0.y, v0.z, v0.w);
-    reg = crc32c::crc32c_update_16(L.s, reg, v1.x, v1.y, v1.z, v1.w);
-    reg = crc32c::crc32c_update_16(L.s, reg, v2.x, v2.y, v2.z, v2.w);
-    reg = crc32c::crc32c_update_16(L.s, reg, v3.x, v3.y, v3.z, v3.w);
-  }
-  for (; j < e; ++j) {
-    const u32x4 v = q[j];
-    reg = crc32c::crc32c_update_16(L.s, reg, v.x, v.y, v.z, v.w);
-  }
-  reg = crc32c::crc32c_update_bytes(L.s.t[0], reg, reinterpret_cast<const uint8_t*>(b), tail_n);
-  const bool any = head_n + tail_n + (e - s) * 16 != 0;
-  const uint32_t crc = any ? crc32c::crc32c_shift(L.x2n, ~reg, n - seg_end) : 0u;
-  return wave_xor(crc);
 }
 
 // ---- writing -------------------------------------------------------------------------------------------------
@@ -234,39 +127,12 @@ __global__ void read_reset_kernel(ReadState* st)
   *st = z;
 }
 
-// The window of the chunk at pos < n: ONE 16-byte load, moved back where it would pass the end of the input
-// (its bytes in front of pos are shifted out); an input shorter than that, byte by byte.
-__device__ __forceinline__ Window load_window(cgptr in, uint64_t n, uint64_t pos)
-{
-  Window w;
-  if (n >= 16) {
-    const uint64_t at = n - pos >= 16 ? pos : n - 16;
-    const u32x4 v = load_u128_any(in + at);
-    uint64_t lo = (uint64_t)v.x | (uint64_t)v.y << 32, hi = (uint64_t)v.z | (uint64_t)v.w << 32;
-    uint32_t drop = (uint32_t)(pos - at);
-    if (drop >= 8) {
-      lo = hi;
-      hi = 0;
-      drop -= 8;
-    }
-    if (drop) {
-      lo = lo >> (8 * drop) | hi << (64 - 8 * drop);
-      hi >>= 8 * drop;
-    }
-    w.lo = lo;
-    w.hi = hi;
-  } else {
-    for (uint32_t k = 0; pos + k < n; ++k)
-      (k < 8 ? w.lo : w.hi) |= (uint64_t)in[pos + k] << (8 * (k & 7u));
-  }
-  return w;
-}
-
 // One lane: the chain is serial by the format's construction.  Between two calls the walk stands in front of a
 // chunk or at the end of the input.  A pass ends in front of the data chunk that does not fit it any more, so what
 // lies between and behind the data chunks (identifiers, padding) is passed with the chunks before it.
 // lists: false counts only and goes to the end.
-__global__ void read_walk_kernel(const uint8_t* in_, uint64_t n, ReadState* stp, ReadLists l, bool lists, uint32_t capacity)
+__device__ __forceinline__ void read_walk(const uint8_t* in_, uint64_t n, ReadState* stp, ReadLists l, bool lists,
+                                          uint32_t capacity)
 {
   cgptr in = to_global(in_);
   ReadState st = *stp;
@@ -312,7 +178,24 @@ __global__ void read_walk_kernel(const uint8_t* in_, uint64_t n, ReadState* stp,
       l.flags[i] = kEntryStored | kEntryFailed;
     }
   }
+  st.walked += count; // (the data chunks this call stepped over)
   *stp = st;
+}
+
+__global__ void read_walk_kernel(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists, uint32_t capacity)
+{
+  read_walk(in, n, stp, l, lists, capacity);
+}
+
+// The walk behind the passes of an indexed read (snappy_frame_index_launch.hpp): where they listed and placed
+// everything, *skip says so and nothing is left to do here.  (A kernel of its own: the walk of a stream without an
+// index is the kernel above, without a word to load and test.)
+__global__ void read_walk_unless_kernel(const uint8_t* in, uint64_t n, ReadState* stp, ReadLists l, bool lists,
+                                        uint32_t capacity, const uint32_t* skip)
+{
+  if (*skip)
+    return;
+  read_walk(in, n, stp, l, lists, capacity);
 }
 
 // ---- reading: places -----------------------------------------------------------------------------------------
@@ -462,9 +345,13 @@ hipError_t launch_read_reset(ReadState* st, hipStream_t stream)
 }
 
 hipError_t launch_read_walk(const uint8_t* in, uint64_t in_bytes, ReadState* st, const ReadLists* lists, uint32_t capacity,
-                            hipStream_t stream)
+                            hipStream_t stream, const uint32_t* skip)
 {
-  read_walk_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity);
+  if (skip)
+    read_walk_unless_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity,
+                                                 skip);
+  else
+    read_walk_kernel<<<1, 1, 0, stream>>>(in, in_bytes, st, lists ? *lists : ReadLists(), lists != nullptr, capacity);
   return hipGetLastError();
 }
 

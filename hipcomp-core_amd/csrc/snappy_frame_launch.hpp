@@ -58,6 +58,7 @@ struct ReadState
   uint32_t done;       // the walk stands at the end of the input
   uint32_t count;      // entries of this pass
   uint32_t verdict;    // kVerdict* bits
+  uint32_t walked;     // data chunks the walk stepped over since the reset: each call adds its own count once
 };
 
 // The entries of a pass, one per data chunk (device memory, the manager's scratch).
@@ -77,9 +78,10 @@ constexpr size_t kReadEntryBytes = 5 * 8 + 4 * 4;
 
 hipError_t launch_read_reset(ReadState* st, hipStream_t stream);
 // Follows the chain from where the last pass stopped until `capacity` data chunks are listed and the next one shows,
-// or to the end of the input; lists == nullptr: to the end, counting only.
+// or to the end of the input; lists == nullptr: to the end, counting only.  skip (device memory): where *skip is set
+// the call does nothing -- the walk behind an indexed read's passes (snappy_frame_index_launch.hpp).
 hipError_t launch_read_walk(const uint8_t* in, uint64_t in_bytes, ReadState* st, const ReadLists* lists, uint32_t capacity,
-                            hipStream_t stream);
+                            hipStream_t stream, const uint32_t* skip = nullptr);
 // out_ptrs[] and batch_caps[] from a scan of content[] that continues from st->out_cursor; an entry without room in
 // out[0, out_bytes) is failed and asks nothing of the decoder
 hipError_t launch_read_scan(const ReadLists& l, ReadState* st, uint8_t* out, uint64_t out_bytes, hipStream_t stream);

@@ -16,6 +16,13 @@ struct SnappyFormatSpecHeader
   /* empty, as in the reference: one byte of the container */
 };
 
+/* where compress_frame puts the chunk index of a seekable framed stream: nowhere, or behind the stream identifier */
+enum class SnappyFrameIndex
+{
+  None,
+  Leading
+};
+
 struct SnappyManager : hipcompManagerBase
 {
   /* device_id must be the current device */
@@ -75,6 +82,42 @@ struct SnappyManager : hipcompManagerBase
   DecompressionConfig configure_frame_decompression(const uint8_t* frames, size_t frames_bytes);
   void decompress_frame(uint8_t* decomp_buffer, const uint8_t* frames, size_t frames_bytes,
                         const DecompressionConfig& decomp_config);
+
+  /* ---- Seekable Snappy framed streams: a chunk index in a reserved skippable chunk behind the identifier ----
+     INTEGRATION.md, "Seekable Snappy framed streams", has the layout, the contract and the fallback rule.
+     Writing: SnappyFrameIndex::None is the call above, byte for byte.  Leading writes, behind the identifier, one
+     chunk of the reserved skippable type 0xa5 -- "HCSNPIDX", version, flags, uncomp_chunk_size, num_chunks, the
+     content size, the first four bytes of every data chunk as they stand in the stream, a masked CRC-32C: 40 +
+     4 * num_chunks bytes -- and behind it the very data chunks the call above writes.  Readers elsewhere step over
+     the chunk: the result is still a plain .sz file.  max_compressed_buffer_size is the bound above plus 40 +
+     4 * num_chunks, *frame_bytes counts the index.  More than 4 194 294 chunks do not fit the chunk's length
+     field: hipcompErrorInvalidValue and sizes 0, like uncomp_chunk_size > 65536.
+     Reading: configure_frame_decompression and decompress_frame find the index themselves.  Where `frames` is
+     streams of the form written here and nothing else but padding and skippable chunks between them, the data
+     chunks are found by a scan of the index, not by following the chain.  The index is not trusted: it is used
+     only where every word is found at its scanned place in the stream, with a type, length and preamble that fit
+     the chunk's share of the content, and every compressed chunk decodes to exactly that share; in every other
+     case the call carries on as if the index were any skippable chunk, with the status, size and bytes it has
+     without it. */
+  CompressionConfig configure_frame_compression(size_t decomp_buffer_size, SnappyFrameIndex index);
+  void compress_frame(const uint8_t* decomp_buffer, uint8_t* frame, const CompressionConfig& comp_config,
+                      size_t* frame_bytes, SnappyFrameIndex index);
+  /* Bytes [first_byte, first_byte + num_bytes) of the content decompress_frame would produce for `frames` into
+     out[0, num_bytes): only the data chunks the range touches are read, decoded or copied and, under a verifying
+     policy, checked -- each of them whole -- against their CRCs.  `frames` has to be streams as written with
+     SnappyFrameIndex::Leading -- up to 32 of them, padding and skippable chunks between them -- and every index has
+     to be found in its stream, word for word: anything else is hipcompErrorNotSupported with nothing written to
+     out, as is an index of chunks so large that two of them do not fit this manager's scratch space.  A range that
+     ends beyond decomp_data_size: hipcompErrorInvalidValue; num_bytes == 0 succeeds and launches nothing.  A
+     touched chunk that does not decode to its share: hipcompErrorCannotDecompress, a CRC that does not fit:
+     hipcompErrorBadChecksum; chunks the range does not touch are not looked at.  Reads stay inside
+     frames[0, frames_bytes), writes inside out[0, num_bytes) and the scratch.  The call synchronises the stream
+     once: the host reads the table of streams the device made. */
+  void decompress_frame_range(uint8_t* out, const uint8_t* frames, size_t frames_bytes,
+                              const DecompressionConfig& decomp_config, size_t first_byte, size_t num_bytes);
+  /* the data chunks the last decompress_frame found by following the chain: 0 where the index served, num_chunks
+     where there was none or it was refused (synchronises the stream) */
+  size_t get_frame_walked_chunks();
 
 private:
   struct Impl;
