@@ -16,6 +16,7 @@
 // constant of the manager, as in the reference.
 #include "cascaded_launch.hpp"
 #include "checksum_launch.hpp"
+#include "gather_launch.hpp"
 #include "hlif_container.hpp"
 #include "host_common.hpp"
 #include "lz4_frame_index_launch.hpp"
@@ -264,6 +265,8 @@ struct Core
     if (own_scratch)
       (void)hipFree(scratch);
     (void)hipHostFree(header_host);
+    if (ranges_head_host)
+      (void)hipHostFree(ranges_head_host);
   }
   Core(const Core&) = delete;
   Core& operator=(const Core&) = delete;
@@ -718,6 +721,184 @@ struct Core
                                 stream),
             "decompress_range: checksums");
     check(hipGetLastError(), "decompress_range kernels");
+  }
+
+  // ---- many ranges in one call: range r of the buffer into out[off[r], off[r] + num[r]) ----
+  // The arithmetic is gather_plan.hpp's, the kernels gather_kernels.hip's.  The ranges stay on the device: a plan
+  // (check and scan, mark, rank) decides there whether the call is refused and numbers the chunks some range
+  // touches; the host fetches four words of it -- the call's one synchronisation -- and enqueues the passes.  A pass
+  // decodes up to S touched chunks whole, each once, into a scratch slot of its own (list, batched decoder,
+  // verdict, checksums: as decompress_range does for its edge chunks) and the copy kernels hand every range its
+  // pieces.  The scratch, carved out of what scratch_bytes() promises: the head, the LZ4 decoder's ticket words,
+  // the CrcState, the call's tables, S slots, the lists of S chunks.
+  static constexpr size_t kRangesOwnSlots = 1024; // what the manager's own scratch holds (the caller's: what fits)
+  hipcomp::RangesStats ranges_stats = {};
+  GatherHead* ranges_head_host = nullptr; // pinned
+  size_t ranges_room(size_t tables) const
+  {
+    if (scratch && !own_scratch)
+      return scratch_bytes();
+    const size_t want = (size_t)gather::room_of(kRangesOwnSlots, range_slot_stride(), tables), all = scratch_bytes();
+    return want < all ? want : all;
+  }
+  size_t ranges_pass_chunks() const
+  {
+    return (size_t)gather::slots_of(ranges_room(0), range_slot_stride(), 0, kPlacedSlab);
+  }
+
+  void decompress_ranges(uint8_t* out, size_t out_bytes, const uint8_t* comp_buffer, const hipcomp::DecompressionConfig& cfg,
+                         const size_t* device_first_bytes, const size_t* device_num_bytes, size_t num_ranges,
+                         size_t* device_out_offsets)
+  {
+    // (a configuration refused by configure_decompression: nothing to do, its status stands)
+    if (cfg.num_chunks == 0 && cfg.decomp_data_size == 0 && *cfg.get_status() == hipcompErrorCannotDecompress)
+      return;
+    ranges_stats = hipcomp::RangesStats();
+    if (num_ranges == 0) {
+      *cfg.get_status() = hipcompSuccess;
+      return;
+    }
+    if (num_ranges >= 0xFFFFFFFFull)
+      throw std::runtime_error("decompress_ranges: more than 2^32 - 2 ranges");
+    const size_t stride = range_slot_stride();
+    // (the bitmap has a bit per chunk the configured size has, whatever num_chunks says: a range inside
+    // decomp_data_size stays inside it; a num_chunks that differs fails the header test)
+    // (at least one word of it, for a buffer of no bytes and ranges of none)
+    const uint64_t whole_chunks = ((uint64_t)cfg.decomp_data_size + chunk_bytes - 1) / chunk_bytes;
+    const uint64_t bitmap_chunks = whole_chunks ? whole_chunks : 1;
+    const size_t tables = (size_t)gather::table_bytes(num_ranges, bitmap_chunks);
+    const size_t room = ranges_room(tables);
+    const size_t S = (size_t)gather::slots_of(room, stride, tables, kPlacedSlab);
+    if (S < 2)
+      throw std::runtime_error("decompress_ranges: the scratch space does not hold the tables and two chunks of this size");
+    if (!ranges_head_host)
+      check(hipHostMalloc((void**)&ranges_head_host, sizeof(GatherHead), hipHostMallocDefault), "hipHostMalloc(ranges)");
+    uint8_t* const s = ensure_scratch(room);
+    uint8_t* at = checksum_area(s);
+    const auto carve = [&at](size_t bytes) {
+      uint8_t* const p = at;
+      at += gather::round16(bytes);
+      return p;
+    };
+    GatherCall g;
+    g.first = device_first_bytes;
+    g.num = device_num_bytes;
+    g.ranges = num_ranges;
+    g.decomp_bytes = cfg.decomp_data_size;
+    g.chunk_bytes = chunk_bytes;
+    g.elem = codec == Cascaded ? (uint32_t)cascaded_elem : 1u;
+    g.words = gather::bitmap_words(bitmap_chunks);
+    g.head = reinterpret_cast<GatherHead*>(carve(64));
+    uint8_t* const ticket = carve(64); // (the LZ4 decoder's chunk ticket counter)
+    CrcState* const crc_state = reinterpret_cast<CrcState*>(carve(64));
+    g.offs = reinterpret_cast<uint64_t*>(carve(8 * (num_ranges + 1)));
+    g.long_list = reinterpret_cast<uint32_t*>(carve(4 * num_ranges));
+    g.bitmap = reinterpret_cast<uint32_t*>(carve(4 * g.words));
+    g.word_rank = reinterpret_cast<uint32_t*>(carve(4 * g.words));
+    g.group_rank = reinterpret_cast<uint32_t*>(carve(4 * ((g.words + gather::kRankGroup - 1) / gather::kRankGroup)));
+    RangeSlots slots;
+    slots.base = carve(S * stride);
+    slots.stride = stride;
+    GatherLists l;
+    l.comp_ptrs = reinterpret_cast<const uint8_t**>(at);
+    l.comp_sizes = reinterpret_cast<size_t*>(at + S * 8);
+    l.caps = reinterpret_cast<size_t*>(at + S * 16);
+    l.out_ptrs = reinterpret_cast<uint8_t**>(at + S * 24);
+    l.actual = reinterpret_cast<size_t*>(at + S * 32);
+    l.statuses = reinterpret_cast<hipcompStatus_t*>(at + S * 40);
+    l.comp_sums = reinterpret_cast<uint32_t*>(at + S * 44);
+    l.decomp_sums = reinterpret_cast<uint32_t*>(at + S * 48);
+    const size_t n = cfg.num_chunks;
+    const Layout lay = layout(n);
+    RangeContainer rc;
+    rc.container = comp_buffer;
+    rc.offsets_at = lay.offsets;
+    rc.data_at = lay.data;
+    rc.num_chunks = n;
+    rc.format = format;
+    check(gather_launch_plan(g, rc, out_bytes, device_out_offsets, cfg.get_status(), stream), "decompress_ranges: plan");
+    check(hipMemcpyAsync(ranges_head_host, g.head, sizeof(GatherHead), hipMemcpyDeviceToHost, stream),
+          "decompress_ranges: plan");
+    check(hipStreamSynchronize(stream), "decompress_ranges: plan");
+    const GatherHead head = *ranges_head_host;
+    ranges_stats.ranges = num_ranges;
+    ranges_stats.total_bytes = (size_t)head.total_bytes;
+    if (head.refused || head.header_bad || head.touched == 0)
+      return;
+    const uint64_t passes = gather::passes_of(head.touched, S);
+    ranges_stats.touched_chunks = head.touched;
+    ranges_stats.passes = (size_t)passes;
+    const bool* const comp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_comp_buffer_checksums));
+    const bool* const decomp_flag =
+        reinterpret_cast<const bool*>(comp_buffer + offsetof(CommonHeader, include_per_chunk_decomp_buffer_checksums));
+    if (verifies())
+      check(crc_launch_reset(crc_state, stream), "decompress_ranges: checksums");
+    for (uint64_t k = 0; k < passes; ++k) {
+      const uint32_t count = (uint32_t)gather::pass_count(head.touched, S, k);
+      check(gather_launch_list(g, rc, lay.sizes, lay.comp_checksums, lay.decomp_checksums, S, k, count, slots, l,
+                               cfg.get_status(), stream),
+            "decompress_ranges: chunk list");
+      switch (codec) {
+      case LZ4:
+        check(lz4_launch_decompress(l.comp_ptrs, l.comp_sizes, l.caps, count, l.out_ptrs, l.actual, l.statuses, true, stream,
+                                    ticket, 64),
+              "LZ4Manager::decompress_ranges");
+        break;
+      case Snappy:
+        if (hipcompBatchedSnappyDecompressAsync(reinterpret_cast<const void* const*>(l.comp_ptrs), l.comp_sizes, l.caps,
+                                                l.actual, count, nullptr, 0, reinterpret_cast<void* const*>(l.out_ptrs),
+                                                l.statuses, stream)
+            != hipcompSuccess)
+          throw std::runtime_error("SnappyManager::decompress_ranges: batched decompress failed");
+        break;
+      case Cascaded:
+        if (hipcompBatchedCascadedDecompressAsync(reinterpret_cast<const void* const*>(l.comp_ptrs), l.comp_sizes, l.caps,
+                                                  l.actual, count, nullptr, 0, reinterpret_cast<void* const*>(l.out_ptrs),
+                                                  l.statuses, stream)
+            != hipcompSuccess)
+          throw std::runtime_error("CascadedManager::decompress_ranges: batched decompress failed");
+        break;
+      }
+      slab_verdict_kernel<<<(count + kBlock - 1) / kBlock, kBlock, 0, stream>>>(l.statuses, l.actual, l.caps, count,
+                                                                                  cfg.get_status());
+      if (verifies()) {
+        // per chunk only, as in decompress_range; the stored values are the pass's gathered lists
+        CrcChunks in;
+        in.ptrs = l.comp_ptrs;
+        in.lens = l.comp_sizes;
+        in.caps = l.caps;
+        in.count = count;
+        CrcTarget in_t;
+        in_t.stored = l.comp_sums;
+        in_t.present = comp_flag;
+        in_t.pass_bytes = slot_bytes;
+        in_t.pass_word = &crc_state->comp_pass;
+        in_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(in, in_t, stream), "decompress_ranges: checksums");
+        CrcChunks dec;
+        dec.ptrs = l.out_ptrs;
+        dec.lens = l.actual;
+        dec.caps = l.caps;
+        dec.clamp_to_caps = true;
+        dec.count = count;
+        CrcTarget dec_t;
+        dec_t.stored = l.decomp_sums;
+        dec_t.present = decomp_flag;
+        dec_t.stride = chunk_bytes;
+        dec_t.pass_bytes = (uint64_t)count * chunk_bytes;
+        dec_t.pass_word = &crc_state->decomp_pass;
+        dec_t.flags = &crc_state->flags;
+        check(crc_launch_chunks(dec, dec_t, stream), "decompress_ranges: checksums");
+      }
+      check(gather_launch_copy(g, out, S, k, count, head.long_ranges, head.long_span, slots, l, stream),
+            "decompress_ranges: copy");
+    }
+    if (verifies())
+      check(range_launch_finish(comp_flag, decomp_flag, crc_state, policy == hipcomp::ComputeAndVerify, cfg.get_status(),
+                                stream),
+            "decompress_ranges: checksums");
+    check(hipGetLastError(), "decompress_ranges kernels");
   }
 
   // ---- LZ4 frames (hipcomp/lz4.hpp; the format: lz4_frame.hpp; the kernels: lz4_frame_launch.hpp) ----
@@ -1523,7 +1704,16 @@ hipcompStatus_t* DecompressionConfig::get_status() const { return status.get(); 
                            size_t num_bytes)                                                                        \
   {                                                                                                                 \
     impl->core.decompress_range(out, comp, c, first_byte, num_bytes);                                               \
-  }
+  }                                                                                                                 \
+  void M::decompress_ranges(uint8_t* out, size_t out_bytes, const uint8_t* comp, const DecompressionConfig& c,      \
+                            const size_t* device_first_bytes, const size_t* device_num_bytes, size_t num_ranges,    \
+                            size_t* device_out_offsets)                                                             \
+  {                                                                                                                 \
+    impl->core.decompress_ranges(out, out_bytes, comp, c, device_first_bytes, device_num_bytes, num_ranges,         \
+                                 device_out_offsets);                                                               \
+  }                                                                                                                 \
+  size_t M::get_ranges_pass_chunks() const { return impl->core.ranges_pass_chunks(); }                              \
+  RangesStats M::get_ranges_stats() const { return impl->core.ranges_stats; }
 
 struct LZ4Manager::Impl
 {

@@ -43,6 +43,14 @@ struct CascadedManager : hipcompManagerBase
      the range touches are read, decoded and checked (hipcompManager.hpp, "Ranged reads") */
   void decompress_range(uint8_t* out, const uint8_t* comp_buffer, const DecompressionConfig& decomp_config,
                         size_t first_byte, size_t num_bytes);
+  /* many ranges in one call, the ranges in device memory: range r into out[off[r], off[r] + num[r]), off the
+     exclusive sum of the lengths; every chunk some range touches is decoded and checked once (hipcompManager.hpp,
+     "Reading many ranges").  A first or a length that is not whole elements refuses the call. */
+  void decompress_ranges(uint8_t* out, size_t out_bytes, const uint8_t* comp_buffer, const DecompressionConfig& decomp_config,
+                         const size_t* device_first_bytes, const size_t* device_num_bytes, size_t num_ranges,
+                         size_t* device_out_offsets);
+  size_t get_ranges_pass_chunks() const;
+  RangesStats get_ranges_stats() const;
 
 private:
   struct Impl;

@@ -33,6 +33,35 @@
  * are decoded whole into scratch space, so they are checked too); the two full-buffer checksums are not checked.
  * A chunk that fails leaves its part of out as it was.  The scratch space is the manager's
  * (get_required_scratch_buffer_size() is what it was).  INTEGRATION.md has the contract in full.
+ *
+ * Reading many ranges.  The three managers also have a non-virtual
+ *
+ *   void decompress_ranges(uint8_t* out, size_t out_bytes, const uint8_t* comp_buffer, const DecompressionConfig& cfg,
+ *                          const size_t* device_first_bytes, const size_t* device_num_bytes, size_t num_ranges,
+ *                          size_t* device_out_offsets);   // may be null; num_ranges + 1 entries
+ *
+ * for the rows a filter selected or the values behind a list of offsets.  The two range arrays lie in device
+ * memory and the host never reads them.  Range r is bytes [first[r], first[r] + num[r]) of the uncompressed
+ * buffer; the ranges land in out back to back in the order given, range r at off[r], the exclusive sum of the
+ * lengths in front of it, and where device_out_offsets is given off[0 .. num_ranges] is written there (the last
+ * entry: the total).  Ranges may be empty, overlap, repeat and come in any order; out may lie at any alignment.
+ * A range decompress_range would refuse, or a total above out_bytes, refuses the whole call:
+ * hipcompErrorInvalidValue, no byte of out or of device_out_offsets written (the decision is a word on the
+ * device).  A header that contradicts cfg: hipcompErrorCannotDecompress, nothing written either.  Every chunk
+ * some range touches is decoded once per call, whole, into scratch space and, under a verifying policy, checked on
+ * both sides once; the status is decompress_range's.  A chunk that fails gives nothing to the ranges that touch
+ * it (their bytes are unspecified but inside out[0, total)); every other range holds exactly its bytes.
+ * num_ranges == 0 is success and launches nothing.  Otherwise the call synchronises the stream ONCE, after its
+ * plan, to learn how many passes to enqueue: it cannot be captured into a graph.  The scratch space is the
+ * manager's (get_required_scratch_buffer_size() is what it was) and also holds the call's tables, about
+ * 12 bytes per range and a byte per 4 chunks; a scratch that cannot hold them and two chunks makes the call throw.
+ *
+ *   size_t get_ranges_pass_chunks() const;   // distinct chunks one pass decodes with the scratch the manager has
+ *                                            // now (before a call's tables take their share of a caller's buffer)
+ *   RangesStats get_ranges_stats() const;    // of the last call: what its one synchronisation fetched
+ *
+ * There is no such call for frames and no C binding.  It is built for many small ranges; for a few large ones
+ * decompress_range, which decodes interior chunks straight into out, stays the better call.
  */
 #ifndef HIPCOMP_MANAGER_HPP
 #define HIPCOMP_MANAGER_HPP
@@ -85,6 +114,17 @@ struct DecompressionConfig
 
 private:
   std::shared_ptr<hipcompStatus_t> status;
+};
+
+/* what the last decompress_ranges of a manager found (host values, no synchronisation): the ranges it was given,
+   the distinct chunks they touch (each decoded once), the passes that took, the sum of the lengths.  A refused
+   call, or one whose header check failed, has 0 touched chunks and 0 passes. */
+struct RangesStats
+{
+  size_t ranges;
+  size_t touched_chunks;
+  size_t passes;
+  size_t total_bytes;
 };
 
 struct hipcompManagerBase
