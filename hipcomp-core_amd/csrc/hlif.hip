@@ -21,6 +21,7 @@
 #include "host_common.hpp"
 #include "lz4_frame_index_launch.hpp"
 #include "lz4_frame_launch.hpp"
+#include "lz4_frames_launch.hpp"
 #include "lz4_launch.hpp"
 #include "range_launch.hpp"
 #include "snappy_frame_index_launch.hpp"
@@ -1188,6 +1189,92 @@ struct Core
     check(hipGetLastError(), "decompress_frame kernels");
   }
 
+  // ---- a batch of frames in one call (hipcomp/lz4.hpp, decompress_frames; the arithmetic: lz4_frames_plan.hpp; the
+  // kernels: lz4_frames_launch.hpp) ----
+  // Every item has a walk's state of its own at the head of the scratch space.  The first walk counts every item's
+  // data blocks, a scan numbers them through the batch, and the host reads the totals: the one synchronisation.
+  // Then passes of as many blocks as the lists behind the states hold, whatever items they belong to; each is a
+  // pass of decompress_frame with the verdicts going to the entries' items.  decode == false: the size query, the
+  // passes stop behind the placing scan.
+  // The manager's own scratch is grown to the states and kFramesOwnEntries entries; the caller's is scratch_bytes().
+  static constexpr size_t kFramesOwnEntries = 65536;
+  size_t frames_pass_limit = 0; // (set_frames_pass_entries: tests and measurements bound a pass with it; 0: no bound)
+  hipcomp::LZ4FramesStats frames_stats = {};
+  void frames_call(const uint8_t* const* item_ptrs, const size_t* item_bytes, uint8_t* const* out_ptrs, const size_t* out_caps,
+                   size_t* sizes, hipcompStatus_t* statuses, size_t num_items, lz4fb::Prefix prefix, bool decode, const char* who)
+  {
+    frames_stats = hipcomp::LZ4FramesStats();
+    if (num_items == 0)
+      return;
+    if (num_items > lz4fb::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (!item_ptrs || !item_bytes || !sizes || (decode && (!out_ptrs || !out_caps || !statuses)))
+      throw std::runtime_error(std::string(who) + ": a null array");
+    lz4fb::Batch b;
+    b.item_ptrs = item_ptrs;
+    b.item_bytes = item_bytes;
+    b.out_ptrs = decode ? out_ptrs : nullptr;
+    b.out_capacities = decode ? out_caps : nullptr;
+    b.items = num_items;
+    b.prefix = prefix;
+    if (!decode && prefix == lz4fb::kArrowLength) { // the prefixes say it
+      frames_stats.items = num_items;
+      check(lz4fb::launch_prefix_sizes(b, sizes, stream), who);
+      return;
+    }
+    const bool callers = scratch && !own_scratch;
+    const size_t own_need = (size_t)lz4fb::scratch_bytes(num_items, kFramesOwnEntries);
+    const size_t room = callers ? scratch_bytes() : (own_capacity > own_need ? own_capacity : own_need);
+    // (16 bytes of it may go to the alignment of a caller's buffer)
+    size_t P = (size_t)lz4fb::pass_entries(room - 16, num_items, kPlacedSlab);
+    if (P == 0)
+      throw std::runtime_error(std::string(who) + ": the scratch space does not hold the state of the items and two blocks' entries");
+    if (frames_pass_limit && frames_pass_limit < P)
+      P = frames_pass_limit;
+    frames_stats.items = num_items; // (behind everything that throws: a call that threw launched nothing and counts nothing)
+    uint8_t* const s = checksum_area(ensure_scratch(room));
+    lz4fb::Item* const items = reinterpret_cast<lz4fb::Item*>(s);
+    lz4fb::Totals* const totals = reinterpret_cast<lz4fb::Totals*>(s + lz4fb::totals_at(num_items));
+    void* const ticket = s + lz4fb::ticket_at(num_items);
+    const lz4f::ReadLists l = frame_read_lists(s + lz4fb::lists_at(num_items), P);
+    uint32_t* const item_col = reinterpret_cast<uint32_t*>(s + lz4fb::item_column_at(num_items, P));
+    check(lz4fb::launch_begin(b, items, !decode, stream), who);
+    check(lz4fb::launch_scan_items(items, num_items, totals, stream), who);
+    lz4fb::Totals h;
+    check(hipMemcpyAsync(&h, totals, sizeof(h), hipMemcpyDeviceToHost, stream), who);
+    check(hipStreamSynchronize(stream), who);
+    const uint64_t passes = lz4fb::passes_of(h.blocks, P);
+    frames_stats.blocks = (size_t)h.blocks;
+    frames_stats.passes = (size_t)passes;
+    frames_stats.pass_entries = P;
+    for (uint64_t k = 0; k < passes; ++k) {
+      const uint32_t count = (uint32_t)lz4fb::pass_count(h.blocks, P, k);
+      check(lz4fb::launch_list(items, num_items, l, item_col, P, k, decode && verifies(), stream), "frames: walk");
+      check(lz4fb::launch_linked_sizes(l, count, stream), "frames: sizes");
+      check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, nullptr, count, nullptr, l.actual, nullptr, false, stream, ticket,
+                                  64),
+            "frames: sizes");
+      check(lz4fb::launch_place(items, l, item_col, count, k * P, stream), "frames: scan");
+      if (!decode)
+        continue;
+      check(lz4_launch_decompress(l.comp_ptrs, l.batch_bytes, l.batch_caps, count, l.out_ptrs, l.actual, l.statuses, true,
+                                  stream, ticket, 64),
+            "LZ4Manager::decompress_frames");
+      check(lz4fb::launch_batched_verdict(items, l, item_col, count, stream), "frames: verdict");
+      check(lz4fb::launch_stored(l, count, h.largest, stream), "frames: stored blocks");
+      check(lz4fb::launch_linked(items, l, item_col, count, stream), "frames: linked blocks");
+      if (verifies()) {
+        check(lz4fb::launch_block_sums(items, l, item_col, count, stream), "frames: block checksums");
+        check(lz4fb::launch_content_sums(items, l, item_col, count, stream), "frames: content checksums");
+      }
+      check(lz4fb::launch_pass_end(items, l, item_col, count, stream), "frames: pass end");
+    }
+    check(lz4fb::launch_finish(items, num_items, verifies(), policy == hipcomp::ComputeAndVerify, sizes,
+                               decode ? statuses : nullptr, stream),
+          who);
+    check(hipGetLastError(), who);
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -1783,6 +1870,24 @@ void LZ4Manager::decompress_frame_range(uint8_t* out, const uint8_t* frames, siz
 {
   impl->core.decompress_frame_range(out, frames, frames_bytes, c, first_byte, num_bytes);
 }
+void LZ4Manager::decompress_frames(const uint8_t* const* device_item_ptrs, const size_t* device_item_bytes,
+                                   uint8_t* const* device_out_ptrs, const size_t* device_out_capacities,
+                                   size_t* device_actual_bytes, hipcompStatus_t* device_statuses, size_t num_items,
+                                   LZ4FramePrefix prefix)
+{
+  impl->core.frames_call(device_item_ptrs, device_item_bytes, device_out_ptrs, device_out_capacities, device_actual_bytes,
+                         device_statuses, num_items, prefix == LZ4FramePrefix::ArrowLength ? lz4fb::kArrowLength : lz4fb::kNone,
+                         true, "decompress_frames");
+}
+void LZ4Manager::get_frames_decompressed_sizes(const uint8_t* const* device_item_ptrs, const size_t* device_item_bytes,
+                                               size_t* device_decompressed_bytes, size_t num_items, LZ4FramePrefix prefix)
+{
+  impl->core.frames_call(device_item_ptrs, device_item_bytes, nullptr, nullptr, device_decompressed_bytes, nullptr, num_items,
+                         prefix == LZ4FramePrefix::ArrowLength ? lz4fb::kArrowLength : lz4fb::kNone, false,
+                         "get_frames_decompressed_sizes");
+}
+void LZ4Manager::set_frames_pass_entries(size_t entries) { impl->core.frames_pass_limit = entries; }
+LZ4FramesStats LZ4Manager::get_frames_stats() const { return impl->core.frames_stats; }
 void LZ4Manager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
 {
   impl->core.compress_frame(in, frame, c, frame_bytes);

@@ -46,6 +46,9 @@ hipError_t launch_set_size(size_t* word, size_t value, hipStream_t stream);
 
 // ---- reading -------------------------------------------------------------------------------------------------
 constexpr uint32_t kStored = 1, kLinked = 2, kBlockSum = 4, kLast = 8, kContentSum = 16; // + block maximum code << 8
+// (a batch of frames alone, lz4_frames_kernels.hip: the entry is a whole item stored as it is, Arrow's -1, which no
+// block maximum bounds; the walk never sets it)
+constexpr uint32_t kRawItem = 32;
 constexpr uint32_t kVerdictBadChecksum = 1, kVerdictCannotDecompress = 2;
 
 // What the walk keeps between the passes of a call (device memory; the host reads it after configure's walk).

@@ -23,6 +23,24 @@ enum class LZ4FrameIndex
   Leading
 };
 
+/* what stands in front of every item of decompress_frames: nothing, or the eight bytes of an Arrow IPC buffer */
+enum class LZ4FramePrefix
+{
+  None,
+  ArrowLength
+};
+
+/* (test and measurement hook, not a stable interface: see get_frames_stats) what the last decompress_frames /
+   get_frames_decompressed_sizes of a manager found (host values, no synchronisation): the items it was given, the data blocks of all of them, the passes they took and the entries
+   one pass held */
+struct LZ4FramesStats
+{
+  size_t items;
+  size_t blocks;
+  size_t passes;
+  size_t pass_entries;
+};
+
 struct LZ4Manager : hipcompManagerBase
 {
   /* uncomp_chunk_size at most 16 MiB (the LZ4 block limit); device_id must be the current device */
@@ -122,6 +140,45 @@ struct LZ4Manager : hipcompManagerBase
   /* the data blocks the last decompress_frame found by following the chain: 0 where the index served, num_chunks
      where it did not.  Synchronises the stream; meant for tests and for telling why a read was slow. */
   size_t get_frame_walked_blocks();
+
+  /* ---- A batch of LZ4 frames in one call: the buffers of an Arrow IPC record batch, the files of a directory ----
+     INTEGRATION.md, "Batches of LZ4 frames", has the contract in full and a worked Arrow body.
+     Item i is device_item_ptrs[i][0, device_item_bytes[i]), decoded into device_out_ptrs[i][0,
+     device_out_capacities[i]); all six arrays are in device memory, buffers may lie at any byte alignment.
+     LZ4FramePrefix::None: an item is exactly what decompress_frame accepts as `frames` (an index in front of a
+     frame is skipped like any skippable frame: the batch has no index fast path).
+     LZ4FramePrefix::ArrowLength: an item of 0 bytes is an empty buffer (success, size 0); otherwise its first eight
+     bytes are a little-endian int64 p: -1, the remaining bytes are the buffer itself and are copied; p >= 0, the
+     remaining bytes are read as under None and have to decode to exactly p bytes (a p above the capacity is refused
+     before a byte is written); 1 to 7 bytes or p < -1, hipcompErrorCannotDecompress.
+     device_statuses[i] is what decompress_frame says for the item's bytes under this manager's ChecksumPolicy
+     (hipcompErrorBadChecksum before the walk's refusal before hipcompErrorCannotDecompress before
+     hipcompErrorCannotVerifyChecksums -- which an item stored whole gets too under ComputeAndVerify -- before
+     success); device_actual_bytes[i] is the decoded size, 0 for an item that failed (CannotVerifyChecksums is no
+     failure: the bytes are there).  No item's status, size or bytes depend on any other item.  Reads stay inside the
+     items, writes inside each item's capacity and the scratch.
+     get_frames_decompressed_sizes: under ArrowLength the prefix (bytes - 8 for -1) with nothing parsed; under None the
+     sum of the declared content sizes where every frame of the item declares one (a false declaration is returned as
+     declared and refused by the decode), else the size found by a parse -- what configure_frame_decompression
+     gives as decomp_data_size, which is not yet a promise that the item decodes; 0 for an item the walk refuses
+     (a header, a size word or a length that does not fit: what configure_frame_decompression refuses).
+     num_items == 0 launches nothing; more than 2^20 items or a null array throws.  Each call works on the manager's
+     stream and synchronises it once (the host reads how many data blocks the device found); the size query under
+     ArrowLength does not synchronise.  get_required_scratch_buffer_size() is what it was: a pass takes as many blocks
+     as fit, whatever items they belong to.  The manager's own scratch is grown to hold the items' state (160 bytes
+     each); a caller's scratch that cannot hold that and two blocks' entries throws. */
+  void decompress_frames(const uint8_t* const* device_item_ptrs, const size_t* device_item_bytes,
+                         uint8_t* const* device_out_ptrs, const size_t* device_out_capacities, size_t* device_actual_bytes,
+                         hipcompStatus_t* device_statuses, size_t num_items, LZ4FramePrefix prefix);
+  void get_frames_decompressed_sizes(const uint8_t* const* device_item_ptrs, const size_t* device_item_bytes,
+                                     size_t* device_decompressed_bytes, size_t num_items, LZ4FramePrefix prefix);
+  /* TEST AND MEASUREMENT HOOKS, NOT A STABLE INTERFACE: they exist because a caller's scratch buffer has no size
+     argument through which a test could make a pass small, and may change or go in any release; production code has
+     no use for either.  set_frames_pass_entries: at most `entries` block entries per pass of the two calls above
+     (0, the default: as many as the scratch holds).  get_frames_stats: what the last of the two calls found (a call
+     that threw: all zero). */
+  void set_frames_pass_entries(size_t entries);
+  LZ4FramesStats get_frames_stats() const;
 
 private:
   struct Impl;
