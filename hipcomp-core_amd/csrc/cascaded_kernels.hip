@@ -1538,17 +1538,34 @@ __device__ __forceinline__ Runs4 mark_run_starts4(
       good = false;
       return;
     }
-    if (active) {
-      const uint32_t base = incl - lane_total;
-      // A marker is the PADDED index of the run's value in the element buffer, plus one (0: no run starts
-      // here): 16 lane + lane / 2 + k + 1 for run 16 lane + k -- it grows with the run like the run's number
-      // does, and the expansion needs no address arithmetic.  The runs of mine behind the array's last run
-      // start at or behind `total`: their markers go to `total`, behind the output (see the layout note above).
-      const uint32_t first = 16u * (uint32_t)lane + ((uint32_t)lane >> 1) + 1u;
-      marks[base] = (uint16_t)first;
+    // A marker is the PADDED index of the run's value in the element buffer, plus one (0: no run starts
+    // here): 16 lane + lane / 2 + k + 1 for run 16 lane + k -- it grows with the run like the run's number
+    // does, and the expansion needs no address arithmetic.  The runs of mine behind the array's last run
+    // start at or behind `total`: their markers go to `total`, behind the output (see the layout note above).
+    // A run of length 0 (the reference skips it, block_rle_decompress :290-296) starts where the next run
+    // does, and the first run at that position that is not empty owns it.  Which of two markers stored to
+    // one position stays is nothing to build on (the empty runs a lane ENDS in start where the next lane's
+    // first run does, and store later; two lanes may store there in one instruction), so a run of length 0
+    // drops no marker: then no two stores of an array meet at a position of the output.  That is a compare
+    // per run, which the streams of an encoder need not pay for: a length is x + FOR with x >= 0 and no wrap
+    // (above), so only an array whose frame of reference is 0 can hold an empty run at all -- and an
+    // encoder's is its shortest run, 1 at least.  (Wave-uniform: FOR comes from the array's header.)
+    const uint32_t base = incl - lane_total;
+    const uint32_t first = 16u * (uint32_t)lane + ((uint32_t)lane >> 1) + 1u;
+    if (fr != 0u) {
+      if (active) {
+        marks[base] = (uint16_t)first;
+#pragma unroll
+        for (int k = 1; k < 16; ++k)
+          marks[min(base + run[k - 1], total)] = (uint16_t)(first + (uint32_t)k);
+      }
+    } else if (active) {
+      if (run[0] != 0u)
+        marks[base] = (uint16_t)first;
 #pragma unroll
       for (int k = 1; k < 16; ++k)
-        marks[min(base + run[k - 1], total)] = (uint16_t)(first + (uint32_t)k);
+        if (run[k] != run[k - 1])
+          marks[min(base + run[k - 1], total)] = (uint16_t)(first + (uint32_t)k);
     }
   };
   switch (bw) {
@@ -1817,7 +1834,7 @@ __device__ __forceinline__ void cascaded_decode_partition4(
                 const uint32_t incl = wave_scan_add_u32(cv);
                 const uint32_t start = carry + incl - cv;
                 carry += read_lane(incl, 63);
-                if (i < (uint32_t)mm && start < CE)
+                if (cv != 0u && start < CE) // (no marker from a run of length 0, nor behind the array: cv = 0 there)
                   marks[start] = (uint16_t)(i + (i >> 5) + 1u); // (the padded index of the run's value, plus one)
                 too_long = too_long || carry > CE;
               }
@@ -2136,8 +2153,8 @@ __device__ __forceinline__ void cascaded_decode_partition(
         uint32_t o = 0;
         for (int i = 0; i < l; ++i)
           o = ru(o + uniform(meta[i + 1]), 4u);
-        // Each run drops its index+1 at its start position (exclusive prefix
-        // of the lengths) in `marks`; a running max over the positions then
+        // Each run that is not empty drops its index+1 at its start position
+        // (exclusive prefix of the lengths) in `marks`; a running max over the positions then
         // names the run of every output element.  The lengths are used as they
         // come out of the packed array (reference block_read :702-737 +
         // block_bitunpack :563-618; bounds as :712-713).
@@ -2160,8 +2177,8 @@ __device__ __forceinline__ void cascaded_decode_partition(
             const uint32_t incl = wave_scan_add_u32(cv);
             const uint32_t start = carry + incl - cv;
             carry += read_lane(incl, 63);
-            if (i < (uint32_t)n && start < CE)
-              marks[start] = (uint16_t)(i + 1);
+            if (cv != 0u && start < CE) // (no marker from a run of length 0, which starts where the next run does,
+              marks[start] = (uint16_t)(i + 1); //  nor behind the array: cv = 0 there -- one store per position)
             too_long = too_long || carry > CE;
           }
           return true;
@@ -2204,7 +2221,8 @@ __device__ __forceinline__ void cascaded_decode_partition(
         // two 16-byte reads), the running maximum inside the lane on top of the maximum of the lanes
         // below (one wave scan), the values of those runs (E reads), and then either the prefix sum of
         // the delta layer that follows (prefix_store_shifted) or the block as it is, to LDS or to HBM.
-        // (n >= 1 here whenever total > 0: run 1 starts at element 0, so the maximum is never 0 inside `total`.)
+        // (n >= 1 here whenever total > 0: the first run that is not empty starts at element 0, so the maximum
+        // is never 0 inside `total`.)
         uint32_t run_carry = 1; // (>= 1: the lanes behind `total` then read x[0], not x[-1])
         UT sum_carry = head;
         const uint32_t reach = with_delta ? total + 1 : total; // elements of y that are wanted

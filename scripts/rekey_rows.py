@@ -1,4 +1,4 @@
-"""rekey_rows.py OUT.json --added NAME [NAME ...] [--changed NAME [NAME ...] --parent-asm DIR]: carry the newest
+"""rekey_rows.py OUT.json [--added NAME ...] [--changed NAME [NAME ...] --parent-asm DIR] [--remeasured PART.json]: carry the newest
 profiles/rNN_rows.json over to a build that only ADDED kernel objects (csrc/NAME.hip), or changed objects that hold
 none of the measured kernels, without measuring again.
 
@@ -10,8 +10,11 @@ are the same code, instruction for instruction -- and only then writes the same 
 in the table's "_how".  --changed NAME: the object's assembly differs from the table's build, and that is
 allowed only where no kernel the rows name is defined in it (neither in this build's assembly of it nor in the
 parent's); the parent build's assembly of it is read from DIR (its build/*.gfx950.s) so that the table's id can
-still be reproduced from all objects but the added ones.  Anything else (a changed measured kernel) is refused:
-collect again (scripts/collect_profiles.sh)."""
+still be reproduced from all objects but the added ones.  --remeasured PART.json: rows collected again on the build
+at hand (scripts/collect_profiles.sh with ROWS=...; the part must carry this build's ids) replace the table's rows
+of the same names, and only the kernels of the rows that are carried over must be absent from the changed objects.
+Anything else (a changed measured kernel whose row was not collected again) is refused: collect again
+(scripts/collect_profiles.sh)."""
 import argparse
 import glob
 import hashlib
@@ -26,11 +29,17 @@ import bench  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("out")
-ap.add_argument("--added", nargs="+", required=True)
+ap.add_argument("--added", nargs="*", default=[])
 ap.add_argument("--changed", nargs="*", default=[])
 ap.add_argument("--parent-asm")
+ap.add_argument("--remeasured")
 a = ap.parse_args()
+assert a.added or a.changed, "nothing added or changed: the newest table is this build's"
 assert not a.changed or a.parent_asm, "--changed needs --parent-asm DIR"
+part = json.load(open(a.remeasured)) if a.remeasured else {"rows": {}}
+if a.remeasured:
+    assert part.get("kernel_source_sha16") == bench.kernel_source_id() or part.get("device_asm_sha16") == bench.device_asm_id(), (
+        "%s was not measured on the build at hand" % a.remeasured)
 
 tables = sorted(glob.glob(os.path.join(ROOT, "profiles", "r??_rows.json")), reverse=True)
 tables = [t for t in tables if os.path.abspath(t) != os.path.abspath(a.out)]
@@ -48,8 +57,8 @@ for path in files:                       # (bench.device_asm_id over the objects
         text = f.read()
     h.update(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_X", text))
     if name in a.changed:   # none of the measured kernels lives here, before or after
-        measured = {phase["kernel"].split("<")[0] for row in old["rows"].values() for phase in row.values()
-                    if isinstance(phase, dict) and "kernel" in phase}
+        measured = {phase["kernel"].split("<")[0] for key, row in old["rows"].items() if key not in part["rows"]
+                    for phase in row.values() if isinstance(phase, dict) and "kernel" in phase}
         with open(path, "rb") as f:
             both = text + f.read()
         hit = sorted(k for k in measured if re.search(rb"\b%s\b" % re.escape(k.encode()), both))
@@ -59,14 +68,18 @@ if same != old.get("device_asm_sha16"):
     sys.exit("%s was measured on assembly %s; the build at hand without %s has %s: a measured kernel changed, collect again"
              % (tables[0], old.get("device_asm_sha16"), a.added, same))
 new = dict(old)
+new["rows"] = dict(old["rows"])
+new["rows"].update(part["rows"])
 new["_how"] = old["_how"] + (
     "\nCarried over by scripts/rekey_rows.py from %s (sources %s, assembly %s): this build only added %s%s, and the "
     "device assembly of every other kernel object is that table's, instruction for instruction (checked from "
-    "csrc/build/*.gfx950.s); nothing was measured again." % (
+    "csrc/build/*.gfx950.s); %s." % (
         os.path.basename(tables[0]), old.get("kernel_source_sha16"), old.get("device_asm_sha16"),
-        ", ".join("csrc/%s.hip" % n for n in a.added),
-        " and changed %s, which holds none of the measured kernels (checked against the parent build's assembly of it)"
-        % ", ".join("csrc/%s.hip" % n for n in a.changed) if a.changed else ""))
+        ", ".join("csrc/%s.hip" % n for n in a.added) or "nothing",
+        " and changed %s, which holds none of the kernels of the rows carried over (checked against the parent build's "
+        "assembly of it)" % ", ".join("csrc/%s.hip" % n for n in a.changed) if a.changed else "",
+        "the rows %s were measured again on this build, nothing else was" % ", ".join(sorted(part["rows"]))
+        if part["rows"] else "nothing was measured again"))
 new["kernel_source_sha16"] = bench.kernel_source_id()
 new["device_asm_sha16"] = bench.device_asm_id()
 with open(a.out, "w") as f:
