@@ -23,6 +23,7 @@
 #include "lz4_frame_launch.hpp"
 #include "lz4_frames_launch.hpp"
 #include "lz4_launch.hpp"
+#include "parquet_pages_launch.hpp"
 #include "range_launch.hpp"
 #include "snappy_frame_index_launch.hpp"
 #include "snappy_frame_launch.hpp"
@@ -1275,6 +1276,74 @@ struct Core
     check(hipGetLastError(), who);
   }
 
+  // ---- the pages of a batch of Parquet column chunks (hipcomp/snappy.hpp, decompress_parquet_pages; the arithmetic
+  // and the page rules: parquet_pages_plan.hpp; the kernels and the passes: parquet_pages_launch.hpp) ----
+  // What is decided here: the scratch space.  The manager's own is grown to the items' states and kPagesOwnEntries
+  // pages' entries; the caller's is scratch_bytes().
+  static constexpr size_t kPagesOwnEntries = 65536;
+  size_t pages_pass_limit = 0; // (set_parquet_pass_pages: tests and measurements bound a pass with it; 0: no bound)
+  hipcomp::ParquetPagesStats pages_stats = {};
+  static void pages_batch(pqp::Batch& b, const uint8_t* const* chunk_ptrs, const size_t* chunk_bytes, size_t num_chunks,
+                          hipcomp::ParquetCodec codec, const char* who)
+  {
+    if (num_chunks > pqp::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 chunks");
+    if (codec != hipcomp::ParquetCodec::Uncompressed && codec != hipcomp::ParquetCodec::Snappy)
+      throw std::runtime_error(std::string(who) + ": unknown ParquetCodec");
+    b = pqp::Batch();
+    b.chunk_ptrs = chunk_ptrs;
+    b.chunk_bytes = chunk_bytes;
+    b.items = num_chunks;
+    b.codec = codec == hipcomp::ParquetCodec::Snappy ? pqp::kCompressedColumn : pqp::kStoredColumn;
+  }
+  void pages_sizes(const uint8_t* const* chunk_ptrs, const size_t* chunk_bytes, size_t* num_pages, size_t* sizes,
+                   hipcompStatus_t* statuses, size_t num_chunks, hipcomp::ParquetCodec codec)
+  {
+    const char* const who = "get_parquet_pages_sizes";
+    pqp::Batch b;
+    pages_batch(b, chunk_ptrs, chunk_bytes, num_chunks, codec, who);
+    if (num_chunks == 0)
+      return;
+    if (!chunk_ptrs || !chunk_bytes || !num_pages || !sizes || !statuses)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    check(pqp::launch_sizes(b, num_pages, sizes, statuses, stream), who);
+  }
+  void pages_call(const uint8_t* const* chunk_ptrs, const size_t* chunk_bytes, uint8_t* const* out_ptrs, const size_t* out_caps,
+                  size_t* sizes, hipcompStatus_t* statuses, hipcomp::ParquetPageInfo* const* page_ptrs, const size_t* page_caps,
+                  size_t* num_pages, size_t num_chunks, hipcomp::ParquetCodec codec)
+  {
+    const char* const who = "decompress_parquet_pages";
+    static_assert(sizeof(hipcomp::ParquetPageInfo) == sizeof(pqp::Page) && alignof(hipcomp::ParquetPageInfo) == alignof(pqp::Page),
+                  "ParquetPageInfo is the plan's page record");
+    pages_stats = hipcomp::ParquetPagesStats();
+    pqp::Batch b;
+    pages_batch(b, chunk_ptrs, chunk_bytes, num_chunks, codec, who);
+    if (num_chunks == 0)
+      return;
+    if (!chunk_ptrs || !chunk_bytes || !out_ptrs || !out_caps || !sizes || !statuses || !num_pages || (page_ptrs && !page_caps))
+      throw std::runtime_error(std::string(who) + ": a null array");
+    b.out_ptrs = out_ptrs;
+    b.out_capacities = out_caps;
+    b.page_ptrs = reinterpret_cast<pqp::Page* const*>(page_ptrs);
+    b.page_capacities = page_caps;
+    const bool callers = scratch && !own_scratch;
+    const size_t own_need = (size_t)pqp::scratch_bytes(num_chunks, kPagesOwnEntries) + 16;
+    const size_t room = callers ? scratch_bytes() : (own_capacity > own_need ? own_capacity : own_need);
+    // (16 bytes of it may go to the alignment of a caller's buffer)
+    size_t P = (size_t)pqp::pass_entries(room - 16, num_chunks, kPlacedSlab);
+    if (P == 0)
+      throw std::runtime_error(std::string(who) + ": the scratch space does not hold the state of the chunks and two pages' entries");
+    if (pages_pass_limit && pages_pass_limit < P)
+      P = pages_pass_limit;
+    uint8_t* const s = checksum_area(ensure_scratch(room));
+    pqp::Stats found;
+    check(pqp::run(b, sizes, statuses, num_pages, s, P, verifies(), policy == hipcomp::ComputeAndVerify, stream, &found), who);
+    pages_stats.items = num_chunks;
+    pages_stats.pages = (size_t)found.pages;
+    pages_stats.passes = (size_t)found.passes;
+    pages_stats.pass_pages = P;
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -1936,6 +2005,24 @@ void SnappyManager::decompress_frame_range(uint8_t* out, const uint8_t* frames, 
 {
   impl->core.sz_decompress_range(out, frames, frames_bytes, c, first_byte, num_bytes);
 }
+void SnappyManager::get_parquet_pages_sizes(const uint8_t* const* device_chunk_ptrs, const size_t* device_chunk_bytes,
+                                            size_t* device_num_pages, size_t* device_decompressed_bytes,
+                                            hipcompStatus_t* device_statuses, size_t num_chunks, ParquetCodec codec)
+{
+  impl->core.pages_sizes(device_chunk_ptrs, device_chunk_bytes, device_num_pages, device_decompressed_bytes, device_statuses,
+                         num_chunks, codec);
+}
+void SnappyManager::decompress_parquet_pages(const uint8_t* const* device_chunk_ptrs, const size_t* device_chunk_bytes,
+                                             uint8_t* const* device_out_ptrs, const size_t* device_out_capacities,
+                                             size_t* device_actual_bytes, hipcompStatus_t* device_statuses,
+                                             ParquetPageInfo* const* device_page_ptrs, const size_t* device_page_capacities,
+                                             size_t* device_num_pages, size_t num_chunks, ParquetCodec codec)
+{
+  impl->core.pages_call(device_chunk_ptrs, device_chunk_bytes, device_out_ptrs, device_out_capacities, device_actual_bytes,
+                        device_statuses, device_page_ptrs, device_page_capacities, device_num_pages, num_chunks, codec);
+}
+void SnappyManager::set_parquet_pass_pages(size_t pages) { impl->core.pages_pass_limit = pages; }
+ParquetPagesStats SnappyManager::get_parquet_pages_stats() const { return impl->core.pages_stats; }
 void SnappyManager::compress_frame(const uint8_t* in, uint8_t* frame, const CompressionConfig& c, size_t* frame_bytes)
 {
   impl->core.sz_compress(in, frame, c, frame_bytes);

@@ -23,6 +23,35 @@ enum class SnappyFrameIndex
   Leading
 };
 
+/* the codec of a Parquet column, from the file's footer (the caller has it) */
+enum class ParquetCodec
+{
+  Uncompressed,
+  Snappy
+};
+
+/* one listed page of a column chunk, written on the device by decompress_parquet_pages (72 bytes) */
+struct ParquetPageInfo
+{
+  uint64_t header_offset, body_offset;                  /* in the column chunk */
+  uint64_t out_offset;                                  /* of the page's decoded body in the chunk's output */
+  uint32_t compressed_page_size, uncompressed_page_size;
+  uint32_t kind;                                        /* 0 DATA_PAGE, 2 DICTIONARY_PAGE, 3 DATA_PAGE_V2 */
+  uint32_t num_values, encoding;
+  uint32_t rep_levels_bytes, def_levels_bytes;          /* V2; 0 otherwise */
+  uint32_t num_nulls, num_rows;                         /* V2; 0 otherwise */
+  uint32_t crc, flags;                                  /* flags: 1 has_crc, 2 values are stored (not compressed) */
+  uint32_t pad;
+};
+
+/* (test and measurement hook, not a stable interface: see get_parquet_pages_stats) what the last
+   decompress_parquet_pages of a manager found (host values): the items it was given, the listed pages of those that
+   went to the passes, the passes they took and the pages a pass holds */
+struct ParquetPagesStats
+{
+  size_t items, pages, passes, pass_pages;
+};
+
 struct SnappyManager : hipcompManagerBase
 {
   /* device_id must be the current device */
@@ -126,6 +155,43 @@ struct SnappyManager : hipcompManagerBase
   /* the data chunks the last decompress_frame found by following the chain: 0 where the index served, num_chunks
      where there was none or it was refused (synchronises the stream) */
   size_t get_frame_walked_chunks();
+
+  /* ---- The pages of Parquet column chunks, a batch of chunks in one call ----
+     INTEGRATION.md, "Parquet column chunks in the Snappy manager", has the contract in full and a worked example.
+     Item i is one column chunk as it lies in the file: the bytes [first page header, + total_compressed_size), a
+     chain of Thrift compact-protocol PageHeaders with their bodies; `codec` is the column's, from the footer.  The
+     item's output is the decoded bodies of its listed pages -- data pages V1 and V2 and dictionary pages; index pages
+     and pages of unknown kinds are stepped over -- back to back in page order, without the headers; the levels of a
+     V2 page are copied, its values decoded behind them.  device_actual_bytes[i] is the sum of the pages'
+     uncompressed_page_size, device_num_pages[i] the number of listed pages; both are 0 for an item that failed.
+     device_page_ptrs: nullptr, or per item a table of device_page_capacities[i] rows that takes one ParquetPageInfo
+     per listed page; an item with more pages than rows is hipcompErrorInvalidValue and nothing of it is written.
+     hipcompErrorCannotDecompress: a header the Thrift reader or the page rules refuse, a body that runs past the
+     chunk, bytes behind the last page that are no page, an output that does not hold the pages (nothing of the item
+     is written then), a block the batched decoder refuses or that decodes to another size than its header says.
+     Page CRCs (the gzip CRC-32 of the stored body) follow the manager's ChecksumPolicy: compared under a verifying
+     policy -- hipcompErrorBadChecksum, which wins over CannotDecompress --; under ComputeAndVerify an item with a
+     page without one is hipcompErrorCannotVerifyChecksums with its bytes and size in place.
+     All arrays are in device memory; chunks and outputs may lie at any byte alignment (a page table at a
+     ParquetPageInfo's).  No item's status, size, bytes or table depend on any other item.  Reads stay inside the
+     items, writes inside each item's capacity, its table's capacity and the scratch.  get_parquet_pages_sizes is
+     the walk alone and does not synchronise; decompress_parquet_pages synchronises the stream once, to read the
+     number of listed pages of the batch and the size of its largest stored part.  get_required_scratch_buffer_size()
+     is what it was: a pass takes as many pages as fit; a caller's scratch that does not hold the items' states and
+     two pages' entries throws before anything is launched.  At most 2^20 items.  C++ only. */
+  void get_parquet_pages_sizes(const uint8_t* const* device_chunk_ptrs, const size_t* device_chunk_bytes,
+                               size_t* device_num_pages, size_t* device_decompressed_bytes,
+                               hipcompStatus_t* device_statuses, size_t num_chunks, ParquetCodec codec);
+  void decompress_parquet_pages(const uint8_t* const* device_chunk_ptrs, const size_t* device_chunk_bytes,
+                                uint8_t* const* device_out_ptrs, const size_t* device_out_capacities,
+                                size_t* device_actual_bytes, hipcompStatus_t* device_statuses,
+                                ParquetPageInfo* const* device_page_ptrs, const size_t* device_page_capacities,
+                                size_t* device_num_pages, size_t num_chunks, ParquetCodec codec);
+  /* Test and measurement hooks, not a stable interface.  set_parquet_pass_pages: at most `pages` pages per pass of
+     decompress_parquet_pages (0, the default: as many as the scratch holds).  get_parquet_pages_stats: what the last
+     decompress_parquet_pages found (a call that threw counts nothing). */
+  void set_parquet_pass_pages(size_t pages);
+  ParquetPagesStats get_parquet_pages_stats() const;
 
 private:
   struct Impl;
