@@ -23,6 +23,7 @@
 #include "lz4_frame_launch.hpp"
 #include "lz4_frames_launch.hpp"
 #include "lz4_launch.hpp"
+#include "parquet_hybrid_launch.hpp"
 #include "parquet_pages_launch.hpp"
 #include "range_launch.hpp"
 #include "snappy_frame_index_launch.hpp"
@@ -1344,6 +1345,53 @@ struct Core
     pages_stats.pass_pages = P;
   }
 
+  // ---- a batch of Parquet RLE / bit-packed hybrid streams (hipcomp/cascaded.hpp, decode_parquet_hybrid; the
+  // arithmetic and the rules: parquet_hybrid_plan.hpp; the kernel: parquet_hybrid_launch.hpp) ----
+  // One launch on the manager's stream: no scratch, no synchronisation, nothing of the host's read back.
+  void hybrid_call(const uint8_t* const* stream_ptrs, const size_t* stream_bytes, const uint32_t* bit_widths, const size_t* num_values,
+                   void* const* out_ptrs, const size_t* out_caps, size_t* consumed, const uint32_t* match_values, size_t* match_counts,
+                   hipcompStatus_t* statuses, size_t num_items, hipcomp::ParquetHybridForm form, hipcompType_t out_type)
+  {
+    const char* const who = "decode_parquet_hybrid";
+    static_assert((uint32_t)hipcomp::ParquetHybridForm::Bare == pqh::kBare
+                      && (uint32_t)hipcomp::ParquetHybridForm::LengthPrefixed == pqh::kLengthPrefixed
+                      && (uint32_t)hipcomp::ParquetHybridForm::WidthPrefixed == pqh::kWidthPrefixed,
+                  "ParquetHybridForm is the plan's Form");
+    if (num_items > pqh::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (form != hipcomp::ParquetHybridForm::Bare && form != hipcomp::ParquetHybridForm::LengthPrefixed
+        && form != hipcomp::ParquetHybridForm::WidthPrefixed)
+      throw std::runtime_error(std::string(who) + ": unknown ParquetHybridForm");
+    uint32_t element_bytes = 0;
+    switch (out_type) {
+    case HIPCOMP_TYPE_UCHAR: element_bytes = 1; break;
+    case HIPCOMP_TYPE_USHORT: element_bytes = 2; break;
+    case HIPCOMP_TYPE_UINT: element_bytes = 4; break;
+    default: throw std::runtime_error(std::string(who) + ": the elements are UCHAR, USHORT or UINT");
+    }
+    if (num_items == 0)
+      return;
+    if (!stream_ptrs || !stream_bytes || !num_values || !out_ptrs || !out_caps || !statuses
+        || (!bit_widths && form != hipcomp::ParquetHybridForm::WidthPrefixed))
+      throw std::runtime_error(std::string(who) + ": a null array");
+    if ((match_values == nullptr) != (match_counts == nullptr))
+      throw std::runtime_error(std::string(who) + ": the match values and the match counts come together");
+    pqh::Batch b;
+    b.stream_ptrs = stream_ptrs;
+    b.stream_bytes = stream_bytes;
+    b.bit_widths = bit_widths;
+    b.num_values = num_values;
+    b.out_ptrs = out_ptrs;
+    b.out_capacities = out_caps;
+    b.consumed_bytes = consumed;
+    b.match_values = match_values;
+    b.match_counts = match_counts;
+    b.statuses = statuses;
+    b.items = num_items;
+    b.form = (uint32_t)form;
+    check(pqh::launch(b, element_bytes, stream), who);
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -2075,6 +2123,17 @@ CascadedManager::CascadedManager(const hipcompBatchedCascadedOpts_t& options, hi
   impl->core.set_policy(checksum_policy);
 }
 HCAMD_MANAGER_METHODS(CascadedManager)
+void CascadedManager::decode_parquet_hybrid(const uint8_t* const* device_stream_ptrs, const size_t* device_stream_bytes,
+                                            const uint32_t* device_bit_widths, const size_t* device_num_values,
+                                            void* const* device_out_ptrs, const size_t* device_out_capacities,
+                                            size_t* device_consumed_bytes, const uint32_t* device_match_values,
+                                            size_t* device_match_counts, hipcompStatus_t* device_statuses, size_t num_items,
+                                            ParquetHybridForm form, hipcompType_t out_type)
+{
+  impl->core.hybrid_call(device_stream_ptrs, device_stream_bytes, device_bit_widths, device_num_values, device_out_ptrs,
+                         device_out_capacities, device_consumed_bytes, device_match_values, device_match_counts, device_statuses,
+                         num_items, form, out_type);
+}
 
 // reference hipcompManagerFactory.cpp:44-148 (synchronises the stream, as there)
 std::shared_ptr<hipcompManagerBase> create_manager(const uint8_t* comp_buffer, hipStream_t stream, const int device_id)

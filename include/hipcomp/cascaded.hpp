@@ -19,6 +19,14 @@ struct CascadedFormatSpecHeader
   hipcompBatchedCascadedOpts_t options;
 };
 
+/* what stands in front of the runs of an item of decode_parquet_hybrid */
+enum class ParquetHybridForm
+{
+  Bare,           /* the runs alone: the levels of a V2 data page (their length comes from the page table) */
+  LengthPrefixed, /* a 4-byte little-endian byte count, then the runs: the levels of a V1 data page */
+  WidthPrefixed   /* 1 byte bit width, then the runs to the end of the item: dictionary indices */
+};
+
 struct CascadedManager : hipcompManagerBase
 {
   /* device_id must be the current device */
@@ -51,6 +59,23 @@ struct CascadedManager : hipcompManagerBase
                          size_t* device_out_offsets);
   size_t get_ranges_pass_chunks() const;
   RangesStats get_ranges_stats() const;
+  /* A batch of Parquet RLE / bit-packed hybrid streams -- repetition and definition levels, dictionary indices --
+     decoded to UCHAR, USHORT or UINT elements (out_type); every array in device memory.  One launch on the manager's
+     stream: no scratch, no synchronisation, so the arrays may be what an earlier call on the stream leaves behind
+     (a definition-level call's match counts as the num_values of the index call).  Item i writes
+     device_num_values[i] elements; device_consumed_bytes[i] says where the next section of the page begins;
+     device_match_counts[i] counts the decoded values equal to device_match_values[i].  An item the rules refuse is
+     hipcompErrorCannotDecompress with 0 consumed bytes, 0 matches and no byte of its output written; no item's
+     result depends on another's.  Throws before anything is launched: more than 2^20 items, a null mandatory array,
+     one match array without the other, an out_type outside the three.  The contract, rule by rule: INTEGRATION.md,
+     "Parquet levels and dictionary indices in the Cascaded manager". */
+  void decode_parquet_hybrid(const uint8_t* const* device_stream_ptrs, const size_t* device_stream_bytes,
+                             const uint32_t* device_bit_widths, /* per item; ignored (may be null) for WidthPrefixed */
+                             const size_t* device_num_values,   /* values wanted per item */
+                             void* const* device_out_ptrs, const size_t* device_out_capacities, /* in elements */
+                             size_t* device_consumed_bytes,                                     /* may be null */
+                             const uint32_t* device_match_values, size_t* device_match_counts,  /* both null or both set */
+                             hipcompStatus_t* device_statuses, size_t num_items, ParquetHybridForm form, hipcompType_t out_type);
 
 private:
   struct Impl;
