@@ -23,6 +23,7 @@
 #include "lz4_frame_launch.hpp"
 #include "lz4_frames_launch.hpp"
 #include "lz4_launch.hpp"
+#include "parquet_delta_launch.hpp"
 #include "parquet_hybrid_launch.hpp"
 #include "parquet_pages_launch.hpp"
 #include "range_launch.hpp"
@@ -1392,6 +1393,45 @@ struct Core
     check(pqh::launch(b, element_bytes, stream), who);
   }
 
+  // ---- a batch of Parquet DELTA_BINARY_PACKED streams (hipcomp/cascaded.hpp, decode_parquet_delta; the arithmetic and
+  // the rules: parquet_delta_plan.hpp; the kernel: parquet_delta_launch.hpp) ----
+  // One launch on the manager's stream: no scratch, no synchronisation, nothing of the host's read back.
+  void delta_call(const uint8_t* const* stream_ptrs, const size_t* stream_bytes, const size_t* num_values, void* const* out_ptrs,
+                  const size_t* out_caps, size_t* value_counts, size_t* consumed, hipcompStatus_t* statuses, size_t num_items,
+                  hipcomp::ParquetDeltaOutput output, hipcompType_t out_type)
+  {
+    const char* const who = "decode_parquet_delta";
+    static_assert((uint32_t)hipcomp::ParquetDeltaOutput::Values == pqd::kValues
+                      && (uint32_t)hipcomp::ParquetDeltaOutput::Offsets == pqd::kOffsets,
+                  "ParquetDeltaOutput is the plan's Output");
+    if (num_items > pqd::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (output != hipcomp::ParquetDeltaOutput::Values && output != hipcomp::ParquetDeltaOutput::Offsets)
+      throw std::runtime_error(std::string(who) + ": unknown ParquetDeltaOutput");
+    uint32_t element_bytes = 0;
+    switch (out_type) {
+    case HIPCOMP_TYPE_INT: element_bytes = 4; break;
+    case HIPCOMP_TYPE_LONGLONG: element_bytes = 8; break;
+    default: throw std::runtime_error(std::string(who) + ": the elements are INT or LONGLONG");
+    }
+    if (num_items == 0)
+      return;
+    if (!stream_ptrs || !stream_bytes || !out_ptrs || !out_caps || !statuses)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqd::Batch b;
+    b.stream_ptrs = stream_ptrs;
+    b.stream_bytes = stream_bytes;
+    b.num_values = num_values;
+    b.out_ptrs = out_ptrs;
+    b.out_capacities = out_caps;
+    b.value_counts = value_counts;
+    b.consumed_bytes = consumed;
+    b.statuses = statuses;
+    b.items = num_items;
+    b.output = (uint32_t)output;
+    check(pqd::launch(b, element_bytes, stream), who);
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -2133,6 +2173,15 @@ void CascadedManager::decode_parquet_hybrid(const uint8_t* const* device_stream_
   impl->core.hybrid_call(device_stream_ptrs, device_stream_bytes, device_bit_widths, device_num_values, device_out_ptrs,
                          device_out_capacities, device_consumed_bytes, device_match_values, device_match_counts, device_statuses,
                          num_items, form, out_type);
+}
+void CascadedManager::decode_parquet_delta(const uint8_t* const* device_stream_ptrs, const size_t* device_stream_bytes,
+                                           const size_t* device_num_values, void* const* device_out_ptrs,
+                                           const size_t* device_out_capacities, size_t* device_value_counts,
+                                           size_t* device_consumed_bytes, hipcompStatus_t* device_statuses, size_t num_items,
+                                           ParquetDeltaOutput output, hipcompType_t out_type)
+{
+  impl->core.delta_call(device_stream_ptrs, device_stream_bytes, device_num_values, device_out_ptrs, device_out_capacities,
+                        device_value_counts, device_consumed_bytes, device_statuses, num_items, output, out_type);
 }
 
 // reference hipcompManagerFactory.cpp:44-148 (synchronises the stream, as there)

@@ -13,6 +13,7 @@
 // lane l takes value base + l of it, 64 at a time.  No LDS.  Every store is a vector store.
 #include "parquet_hybrid_launch.hpp"
 
+#include "byte_window.hpp"
 #include "device_facts.hpp"
 #include "wave_utils.hpp"
 
@@ -23,26 +24,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-// The register window.  `at` is asked with a wave-uniform position inside the item.
-struct WindowSrc
-{
-  cgptr p;
-  uint64_t n;
-  int lane;
-  uint32_t mine = 0;                 // this lane's byte
-  uint64_t base = uint64_t(1) << 63; // (no position is within 64 of it: the first byte loads the window)
-  __device__ __forceinline__ WindowSrc(cgptr p_, uint64_t n_, int lane_) : p(p_), n(n_), lane(lane_) {}
-  __device__ __forceinline__ uint32_t at(uint64_t pos)
-  {
-    if (pos - base >= (uint64_t)kWave) {
-      base = pos;
-      const uint64_t a = pos + (uint64_t)lane;
-      mine = a < n ? (uint32_t)p[a] : 0u;
-    }
-    return read_lane(mine, (int)uniform((uint32_t)(pos - base)));
-  }
-};
 
 // the element in every place of a dword
 template <class T>

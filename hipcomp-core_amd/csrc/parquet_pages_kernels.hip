@@ -14,6 +14,7 @@
 // Only lane 0 stores.  Every store is a vector store.
 #include "parquet_pages_launch.hpp"
 
+#include "byte_window.hpp"
 #include "checksum_launch.hpp"
 #include "device_facts.hpp"
 #include "lz4_frame_device.hiph"
@@ -74,26 +75,6 @@ Lists lists_of(uint8_t* s, uint64_t items, uint64_t P)
   l.item_col = reinterpret_cast<uint32_t*>(s + list4_at(items, P, 4));
   return l;
 }
-
-// The register window.  `at` is asked with a wave-uniform position inside the chunk.
-struct WindowSrc
-{
-  cgptr p;
-  uint64_t n;
-  int lane;
-  uint32_t mine = 0;                  // this lane's byte
-  uint64_t base = uint64_t(1) << 63; // (no position is within 64 of it: the first byte loads the window)
-  __device__ __forceinline__ WindowSrc(cgptr p_, uint64_t n_, int lane_) : p(p_), n(n_), lane(lane_) {}
-  __device__ __forceinline__ uint32_t at(uint64_t pos)
-  {
-    if (pos - base >= (uint64_t)kWave) {
-      base = pos;
-      const uint64_t a = pos + (uint64_t)lane;
-      mine = a < n ? (uint32_t)p[a] : 0u;
-    }
-    return read_lane(mine, (int)uniform((uint32_t)(pos - base)));
-  }
-};
 
 // what a listing walk does with a page: a row of the table, an entry of the pass (lane 0)
 struct ListSink

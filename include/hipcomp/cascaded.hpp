@@ -27,6 +27,13 @@ enum class ParquetHybridForm
   WidthPrefixed   /* 1 byte bit width, then the runs to the end of the item: dictionary indices */
 };
 
+/* what an item of decode_parquet_delta writes */
+enum class ParquetDeltaOutput
+{
+  Values, /* the decoded integers */
+  Offsets /* the stream holds the lengths of a DELTA_LENGTH_BYTE_ARRAY page: n + 1 Arrow offsets, 0 first */
+};
+
 struct CascadedManager : hipcompManagerBase
 {
   /* device_id must be the current device */
@@ -76,6 +83,23 @@ struct CascadedManager : hipcompManagerBase
                              size_t* device_consumed_bytes,                                     /* may be null */
                              const uint32_t* device_match_values, size_t* device_match_counts,  /* both null or both set */
                              hipcompStatus_t* device_statuses, size_t num_items, ParquetHybridForm form, hipcompType_t out_type);
+  /* A batch of Parquet DELTA_BINARY_PACKED streams -- the values of integer and timestamp pages, or the lengths in
+     front of a DELTA_LENGTH_BYTE_ARRAY page's string bytes -- decoded to INT (Parquet INT32, 32-bit wrapping sums) or
+     LONGLONG (INT64, 64-bit) elements (out_type); every array in device memory.  One launch on the manager's stream:
+     no scratch, no synchronisation, so device_num_values may be the match counts a decode_parquet_hybrid call on the
+     stream leaves behind (the non-null count of the page's definition levels).  Values: item i writes the stream's
+     total count of elements.  Offsets: it writes total + 1 running sums of the lengths, 0 first, and
+     device_consumed_bytes[i] is where the string bytes begin: stream + consumed and the offsets are the Arrow string
+     array.  An item the rules refuse is hipcompErrorCannotDecompress with 0 consumed bytes, a count of 0 and no byte
+     of its output written; no item's result depends on another's.  Throws before anything is launched: more than
+     2^20 items, a null mandatory array, an out_type outside the two, an unknown ParquetDeltaOutput.  The contract,
+     rule by rule: INTEGRATION.md, "Parquet DELTA_BINARY_PACKED values and string offsets in the Cascaded manager". */
+  void decode_parquet_delta(const uint8_t* const* device_stream_ptrs, const size_t* device_stream_bytes,
+                            const size_t* device_num_values, /* may be null: every item decodes its header's count */
+                            void* const* device_out_ptrs, const size_t* device_out_capacities, /* in elements */
+                            size_t* device_value_counts,     /* may be null: the values decoded per item */
+                            size_t* device_consumed_bytes,   /* may be null */
+                            hipcompStatus_t* device_statuses, size_t num_items, ParquetDeltaOutput output, hipcompType_t out_type);
 
 private:
   struct Impl;
