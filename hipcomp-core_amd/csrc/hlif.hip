@@ -24,6 +24,7 @@
 #include "lz4_frames_launch.hpp"
 #include "lz4_launch.hpp"
 #include "parquet_delta_launch.hpp"
+#include "parquet_dict_launch.hpp"
 #include "parquet_hybrid_launch.hpp"
 #include "parquet_pages_launch.hpp"
 #include "range_launch.hpp"
@@ -1432,6 +1433,100 @@ struct Core
     check(pqd::launch(b, element_bytes, stream), who);
   }
 
+  // ---- a Parquet dictionary's entries gathered to rows (hipcomp/cascaded.hpp, index_parquet_dictionary,
+  // gather_parquet_dictionary, gather_parquet_dictionary_strings; the arithmetic and the rules: parquet_dict_plan.hpp;
+  // the kernels: parquet_dict_launch.hpp) ----
+  // One launch each on the manager's stream: no scratch, no synchronisation, nothing of the host's read back.
+  void dict_index_call(const uint8_t* const* dict_ptrs, const size_t* dict_bytes, const size_t* num_entries, int32_t* const* offset_ptrs,
+                       const size_t* offset_caps, size_t* entry_counts, hipcompStatus_t* statuses, size_t num_dicts)
+  {
+    const char* const who = "index_parquet_dictionary";
+    if (num_dicts > pqg::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (num_dicts == 0)
+      return;
+    if (!dict_ptrs || !dict_bytes || !num_entries || !offset_ptrs || !offset_caps || !statuses)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqg::IndexBatch b;
+    b.dict_ptrs = dict_ptrs;
+    b.dict_bytes = dict_bytes;
+    b.num_entries = num_entries;
+    b.offset_ptrs = offset_ptrs;
+    b.offset_capacities = offset_caps;
+    b.entry_counts = entry_counts;
+    b.statuses = statuses;
+    b.items = num_dicts;
+    check(pqg::launch_index(b, stream), who);
+  }
+  // what the two gathers share: the checks of the rows' arrays, and those arrays into the batch
+  static pqg::GatherBatch dict_rows(const char* who, const uint8_t* const* dict_ptrs, const size_t* dict_bytes, const size_t* dict_entries,
+                                    const uint32_t* const* index_ptrs, const size_t* num_indices, const uint8_t* const* level_ptrs,
+                                    const size_t* num_rows, const uint32_t* max_levels, uint8_t* const* validity_ptrs,
+                                    hipcompStatus_t* statuses, size_t num_items)
+  {
+    if (!dict_ptrs || !dict_bytes || !dict_entries || !index_ptrs || !num_indices || !statuses)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    if ((level_ptrs == nullptr) != (num_rows == nullptr) || (level_ptrs == nullptr) != (max_levels == nullptr))
+      throw std::runtime_error(std::string(who) + ": the levels, the rows and the maximum levels come together");
+    pqg::GatherBatch b = {};
+    b.dict_ptrs = dict_ptrs;
+    b.dict_bytes = dict_bytes;
+    b.dict_entries = dict_entries;
+    b.index_ptrs = index_ptrs;
+    b.num_indices = num_indices;
+    b.level_ptrs = level_ptrs;
+    b.num_rows = num_rows;
+    b.max_levels = max_levels;
+    b.validity_ptrs = validity_ptrs;
+    b.statuses = statuses;
+    b.items = num_items;
+    return b;
+  }
+  void dict_gather_call(const uint8_t* const* dict_ptrs, const size_t* dict_bytes, const size_t* dict_entries,
+                        const uint32_t* const* index_ptrs, const size_t* num_indices, const uint8_t* const* level_ptrs,
+                        const size_t* num_rows, const uint32_t* max_levels, void* const* out_ptrs, const size_t* out_caps,
+                        uint8_t* const* validity_ptrs, hipcompStatus_t* statuses, size_t num_items, uint32_t entry_bytes)
+  {
+    const char* const who = "gather_parquet_dictionary";
+    if (num_items > pqg::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (entry_bytes < 1 || entry_bytes > pqg::kMaxEntryBytes)
+      throw std::runtime_error(std::string(who) + ": an entry has 1 to 64 bytes");
+    if (num_items == 0)
+      return;
+    if (!out_ptrs || !out_caps)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqg::GatherBatch b = dict_rows(who, dict_ptrs, dict_bytes, dict_entries, index_ptrs, num_indices, level_ptrs, num_rows, max_levels,
+                                   validity_ptrs, statuses, num_items);
+    b.out_ptrs = out_ptrs;
+    b.out_capacities = out_caps;
+    b.entry_bytes = entry_bytes;
+    check(pqg::launch_gather(b, stream), who);
+  }
+  void dict_strings_call(const uint8_t* const* dict_ptrs, const size_t* dict_bytes, const size_t* dict_entries,
+                         const int32_t* const* dict_offsets, const uint32_t* const* index_ptrs, const size_t* num_indices,
+                         const uint8_t* const* level_ptrs, const size_t* num_rows, const uint32_t* max_levels, int32_t* const* out_offsets,
+                         const size_t* offset_caps, uint8_t* const* out_bytes, const size_t* byte_caps, size_t* out_byte_counts,
+                         uint8_t* const* validity_ptrs, hipcompStatus_t* statuses, size_t num_items)
+  {
+    const char* const who = "gather_parquet_dictionary_strings";
+    if (num_items > pqg::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (num_items == 0)
+      return;
+    if (!dict_offsets || !out_offsets || !offset_caps || !out_bytes || !byte_caps)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqg::GatherBatch b = dict_rows(who, dict_ptrs, dict_bytes, dict_entries, index_ptrs, num_indices, level_ptrs, num_rows, max_levels,
+                                   validity_ptrs, statuses, num_items);
+    b.dict_offsets = dict_offsets;
+    b.out_offsets = out_offsets;
+    b.offset_capacities = offset_caps;
+    b.out_bytes = out_bytes;
+    b.byte_capacities = byte_caps;
+    b.out_byte_counts = out_byte_counts;
+    check(pqg::launch_gather_strings(b, stream), who);
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -2182,6 +2277,39 @@ void CascadedManager::decode_parquet_delta(const uint8_t* const* device_stream_p
 {
   impl->core.delta_call(device_stream_ptrs, device_stream_bytes, device_num_values, device_out_ptrs, device_out_capacities,
                         device_value_counts, device_consumed_bytes, device_statuses, num_items, output, out_type);
+}
+void CascadedManager::index_parquet_dictionary(const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes,
+                                               const size_t* device_num_entries, int32_t* const* device_offset_ptrs,
+                                               const size_t* device_offset_capacities, size_t* device_entry_counts,
+                                               hipcompStatus_t* device_statuses, size_t num_dicts)
+{
+  impl->core.dict_index_call(device_dict_ptrs, device_dict_bytes, device_num_entries, device_offset_ptrs, device_offset_capacities,
+                             device_entry_counts, device_statuses, num_dicts);
+}
+void CascadedManager::gather_parquet_dictionary(const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes,
+                                                const size_t* device_dict_entries, const uint32_t* const* device_index_ptrs,
+                                                const size_t* device_num_indices, const uint8_t* const* device_level_ptrs,
+                                                const size_t* device_num_rows, const uint32_t* device_max_levels,
+                                                void* const* device_out_ptrs, const size_t* device_out_capacities,
+                                                uint8_t* const* device_validity_ptrs, hipcompStatus_t* device_statuses,
+                                                size_t num_items, uint32_t entry_bytes)
+{
+  impl->core.dict_gather_call(device_dict_ptrs, device_dict_bytes, device_dict_entries, device_index_ptrs, device_num_indices,
+                              device_level_ptrs, device_num_rows, device_max_levels, device_out_ptrs, device_out_capacities,
+                              device_validity_ptrs, device_statuses, num_items, entry_bytes);
+}
+void CascadedManager::gather_parquet_dictionary_strings(
+    const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes, const size_t* device_dict_entries,
+    const int32_t* const* device_dict_offsets, const uint32_t* const* device_index_ptrs, const size_t* device_num_indices,
+    const uint8_t* const* device_level_ptrs, const size_t* device_num_rows, const uint32_t* device_max_levels,
+    int32_t* const* device_out_offsets, const size_t* device_offset_capacities, uint8_t* const* device_out_bytes,
+    const size_t* device_byte_capacities, size_t* device_out_byte_counts, uint8_t* const* device_validity_ptrs,
+    hipcompStatus_t* device_statuses, size_t num_items)
+{
+  impl->core.dict_strings_call(device_dict_ptrs, device_dict_bytes, device_dict_entries, device_dict_offsets, device_index_ptrs,
+                               device_num_indices, device_level_ptrs, device_num_rows, device_max_levels, device_out_offsets,
+                               device_offset_capacities, device_out_bytes, device_byte_capacities, device_out_byte_counts,
+                               device_validity_ptrs, device_statuses, num_items);
 }
 
 // reference hipcompManagerFactory.cpp:44-148 (synchronises the stream, as there)

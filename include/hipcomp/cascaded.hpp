@@ -100,6 +100,54 @@ struct CascadedManager : hipcompManagerBase
                             size_t* device_value_counts,     /* may be null: the values decoded per item */
                             size_t* device_consumed_bytes,   /* may be null */
                             hipcompStatus_t* device_statuses, size_t num_items, ParquetDeltaOutput output, hipcompType_t out_type);
+  /* The three calls that turn a dictionary-encoded Parquet column's decoded parts -- the dictionary page's body, the
+     UINT indices and the UCHAR definition levels of decode_parquet_hybrid -- into an Arrow-shaped array: values, or
+     offsets and bytes, and a validity bitmap.  Every array in device memory; each call one launch on the manager's
+     stream, no scratch, no synchronisation, so the counts may be what an earlier call on the stream leaves behind
+     (the levels' match counts as device_num_indices, call 1's entry counts as device_dict_entries).  An item the
+     rules refuse is hipcompErrorCannotDecompress, every count it reports 0 and no byte of its outputs written; no
+     item's result depends on another's.  Each throws before anything is launched: more than 2^20 items, a null
+     mandatory array, a parameter outside its range.  Flat columns, one dictionary per item (many items may name
+     the same one).  The contract, rule by rule: INTEGRATION.md, "Parquet dictionary entries gathered to rows in the
+     Cascaded manager". */
+  /* 1. The Arrow offsets of a PLAIN BYTE_ARRAY dictionary page body (len32 bytes len32 bytes ...): entries + 1
+     of them, 0 first; entry k's bytes lie at dict + 4 * (k + 1) + off[k].  Refused: entries + 1 above the capacity,
+     a body that ends in a length word, a length that runs past the body, a sum above 2^31 - 1. */
+  void index_parquet_dictionary(const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes,
+                                const size_t* device_num_entries, /* the dictionary page's num_values */
+                                int32_t* const* device_offset_ptrs, const size_t* device_offset_capacities, /* in elements */
+                                size_t* device_entry_counts, /* may be null: the entries, 0 of a refused item */
+                                hipcompStatus_t* device_statuses, size_t num_dicts);
+  /* 2. Fixed-width entries (INT32, INT64, FLOAT, DOUBLE, INT96, FIXED_LEN_BYTE_ARRAY) of entry_bytes (1 to 64) each:
+     entry k lies at dict + k * entry_bytes, at any byte address.  Dense (the three arrays of the levels null): row r
+     gets dict[index[r]].  With levels: row r is valid where level[r] == max_level; the j-th valid row gets
+     dict[index[j]], every other row entry_bytes zero bytes.  The validity bitmap is Arrow's, bit r & 7 of byte
+     r >> 3, the unused bits 0; it may lie at any byte address.  The output lies at the alignment of the largest power
+     of two that divides entry_bytes, at most 8.  Refused: rows above the capacity, dict_entries * entry_bytes above
+     dict_bytes, an index at or above dict_entries, a level above max_level, valid rows that are not num_indices. */
+  void gather_parquet_dictionary(const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes,
+                                 const size_t* device_dict_entries, const uint32_t* const* device_index_ptrs,
+                                 const size_t* device_num_indices, const uint8_t* const* device_level_ptrs,
+                                 const size_t* device_num_rows,
+                                 const uint32_t* device_max_levels, /* these three: all null (dense) or all set */
+                                 void* const* device_out_ptrs, const size_t* device_out_capacities, /* in entries (rows) */
+                                 uint8_t* const* device_validity_ptrs, /* may be null; (rows + 7) / 8 bytes per item */
+                                 hipcompStatus_t* device_statuses, size_t num_items, uint32_t entry_bytes);
+  /* 3. BYTE_ARRAY entries to an Arrow string array: rows + 1 offsets, 0 first, a row that is not valid adding 0, and
+     the valid rows' bytes back to back.  device_dict_offsets is what call 1 wrote and is not trusted: an entry an
+     item uses needs 0 <= off[k] <= off[k + 1] and 4 * (k + 1) + off[k + 1] <= dict_bytes.  Refused besides, and
+     besides what call 2 refuses of the rows: rows + 1 above the offset capacity, a byte total above the byte capacity
+     or above 2^31 - 1. */
+  void gather_parquet_dictionary_strings(const uint8_t* const* device_dict_ptrs, const size_t* device_dict_bytes,
+                                         const size_t* device_dict_entries, const int32_t* const* device_dict_offsets,
+                                         const uint32_t* const* device_index_ptrs, const size_t* device_num_indices,
+                                         const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                                         const uint32_t* device_max_levels, /* these three: all null (dense) or all set */
+                                         int32_t* const* device_out_offsets, const size_t* device_offset_capacities, /* elements */
+                                         uint8_t* const* device_out_bytes, const size_t* device_byte_capacities,
+                                         size_t* device_out_byte_counts, /* may be null: the bytes, 0 of a refused item */
+                                         uint8_t* const* device_validity_ptrs, /* may be null */
+                                         hipcompStatus_t* device_statuses, size_t num_items);
 
 private:
   struct Impl;
