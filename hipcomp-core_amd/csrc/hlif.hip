@@ -25,6 +25,7 @@
 #include "lz4_launch.hpp"
 #include "parquet_delta_launch.hpp"
 #include "parquet_dict_launch.hpp"
+#include "parquet_plain_launch.hpp"
 #include "parquet_hybrid_launch.hpp"
 #include "parquet_pages_launch.hpp"
 #include "range_launch.hpp"
@@ -1527,6 +1528,106 @@ struct Core
     check(pqg::launch_gather_strings(b, stream), who);
   }
 
+  // ---- a Parquet page's dense values placed in rows (hipcomp/cascaded.hpp, place_parquet_values,
+  // place_parquet_booleans, place_parquet_strings; the arithmetic and the rules: parquet_plain_plan.hpp; the kernels:
+  // parquet_plain_launch.hpp) ----
+  // One launch each on the manager's stream: no scratch, no synchronisation, nothing of the host's read back.
+  // what the three share: the checks of the source's and the rows' arrays, and those arrays into the batch
+  static pqv::PlaceBatch place_rows(const char* who, const uint8_t* const* src_ptrs, const size_t* src_bytes, const size_t* value_starts,
+                                    const size_t* num_values, const uint8_t* const* level_ptrs, const size_t* num_rows,
+                                    const uint32_t* max_levels, uint8_t* const* validity_ptrs, hipcompStatus_t* statuses, size_t num_items)
+  {
+    if (!src_ptrs || !src_bytes || !num_values || !statuses)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    if ((level_ptrs == nullptr) != (num_rows == nullptr) || (level_ptrs == nullptr) != (max_levels == nullptr))
+      throw std::runtime_error(std::string(who) + ": the levels, the rows and the maximum levels come together");
+    pqv::PlaceBatch b = {};
+    b.src_ptrs = src_ptrs;
+    b.src_bytes = src_bytes;
+    b.value_starts = value_starts;
+    b.num_values = num_values;
+    b.level_ptrs = level_ptrs;
+    b.num_rows = num_rows;
+    b.max_levels = max_levels;
+    b.validity_ptrs = validity_ptrs;
+    b.statuses = statuses;
+    b.items = num_items;
+    return b;
+  }
+  void place_values_call(const uint8_t* const* src_ptrs, const size_t* src_bytes, const size_t* value_starts, const size_t* num_values,
+                         const uint8_t* const* level_ptrs, const size_t* num_rows, const uint32_t* max_levels, void* const* out_ptrs,
+                         const size_t* out_caps, uint8_t* const* validity_ptrs, hipcompStatus_t* statuses, size_t num_items,
+                         uint32_t value_bytes, hipcomp::ParquetValueLayout layout)
+  {
+    const char* const who = "place_parquet_values";
+    static_assert((uint32_t)hipcomp::ParquetValueLayout::Plain == pqv::kPlain
+                      && (uint32_t)hipcomp::ParquetValueLayout::ByteStreamSplit == pqv::kByteStreamSplit,
+                  "ParquetValueLayout is the plan's ValueLayout");
+    if (num_items > pqv::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (value_bytes < 1 || value_bytes > pqv::kMaxValueBytes)
+      throw std::runtime_error(std::string(who) + ": a value has 1 to 64 bytes");
+    if (layout != hipcomp::ParquetValueLayout::Plain && layout != hipcomp::ParquetValueLayout::ByteStreamSplit)
+      throw std::runtime_error(std::string(who) + ": unknown ParquetValueLayout");
+    if (num_items == 0)
+      return;
+    if (!out_ptrs || !out_caps)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqv::PlaceBatch b = place_rows(who, src_ptrs, src_bytes, value_starts, num_values, level_ptrs, num_rows, max_levels, validity_ptrs,
+                                   statuses, num_items);
+    b.out_ptrs = out_ptrs;
+    b.out_capacities = out_caps;
+    b.value_bytes = value_bytes;
+    b.layout = (uint32_t)layout;
+    check(pqv::launch_place_values(b, stream), who);
+  }
+  void place_booleans_call(const uint8_t* const* src_ptrs, const size_t* src_bytes, const size_t* value_starts, const size_t* num_values,
+                           const uint8_t* const* level_ptrs, const size_t* num_rows, const uint32_t* max_levels, uint8_t* const* out_ptrs,
+                           const size_t* out_caps, uint8_t* const* validity_ptrs, hipcompStatus_t* statuses, size_t num_items)
+  {
+    const char* const who = "place_parquet_booleans";
+    if (num_items > pqv::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (num_items == 0)
+      return;
+    if (!out_ptrs || !out_caps)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqv::PlaceBatch b = place_rows(who, src_ptrs, src_bytes, value_starts, num_values, level_ptrs, num_rows, max_levels, validity_ptrs,
+                                   statuses, num_items);
+    b.out_ptrs = reinterpret_cast<void* const*>(out_ptrs);
+    b.out_capacities = out_caps;
+    check(pqv::launch_place_booleans(b, stream), who);
+  }
+  void place_strings_call(const uint8_t* const* body_ptrs, const size_t* body_bytes, const size_t* value_starts,
+                          const int32_t* const* value_offsets, const size_t* num_values, const uint8_t* const* level_ptrs,
+                          const size_t* num_rows, const uint32_t* max_levels, int32_t* const* out_offsets, const size_t* offset_caps,
+                          uint8_t* const* out_bytes, const size_t* byte_caps, size_t* out_byte_counts, uint8_t* const* validity_ptrs,
+                          hipcompStatus_t* statuses, size_t num_items, hipcomp::ParquetStringLayout layout)
+  {
+    const char* const who = "place_parquet_strings";
+    static_assert((uint32_t)hipcomp::ParquetStringLayout::LengthPrefixed == pqv::kLengthPrefixed
+                      && (uint32_t)hipcomp::ParquetStringLayout::Packed == pqv::kPacked,
+                  "ParquetStringLayout is the plan's StringLayout");
+    if (num_items > pqv::kMaxItems)
+      throw std::runtime_error(std::string(who) + ": more than 2^20 items");
+    if (layout != hipcomp::ParquetStringLayout::LengthPrefixed && layout != hipcomp::ParquetStringLayout::Packed)
+      throw std::runtime_error(std::string(who) + ": unknown ParquetStringLayout");
+    if (num_items == 0)
+      return;
+    if (!value_offsets || !out_offsets || !offset_caps || !out_bytes || !byte_caps)
+      throw std::runtime_error(std::string(who) + ": a null array");
+    pqv::PlaceBatch b = place_rows(who, body_ptrs, body_bytes, value_starts, num_values, level_ptrs, num_rows, max_levels, validity_ptrs,
+                                   statuses, num_items);
+    b.value_offsets = value_offsets;
+    b.out_offsets = out_offsets;
+    b.offset_capacities = offset_caps;
+    b.out_bytes = out_bytes;
+    b.byte_capacities = byte_caps;
+    b.out_byte_counts = out_byte_counts;
+    b.layout = (uint32_t)layout;
+    check(pqv::launch_place_strings(b, stream), who);
+  }
+
   // ---- a ranged read of seekable frames: bytes [first_byte, first_byte + num_bytes) of the content into out ----
   // The whole input has to be indexed frames: the hop and the test of every block in its place (no block is read for
   // it but its size word) say so on the device, and the host reads the frame table they leave -- the one
@@ -2310,6 +2411,43 @@ void CascadedManager::gather_parquet_dictionary_strings(
                                device_num_indices, device_level_ptrs, device_num_rows, device_max_levels, device_out_offsets,
                                device_offset_capacities, device_out_bytes, device_byte_capacities, device_out_byte_counts,
                                device_validity_ptrs, device_statuses, num_items);
+}
+void CascadedManager::place_parquet_values(const uint8_t* const* device_value_ptrs, const size_t* device_value_bytes,
+                                           const size_t* device_value_starts, const size_t* device_num_values,
+                                           const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                                           const uint32_t* device_max_levels, void* const* device_out_ptrs,
+                                           const size_t* device_out_capacities, uint8_t* const* device_validity_ptrs,
+                                           hipcompStatus_t* device_statuses, size_t num_items, uint32_t value_bytes,
+                                           ParquetValueLayout layout)
+{
+  impl->core.place_values_call(device_value_ptrs, device_value_bytes, device_value_starts, device_num_values, device_level_ptrs,
+                               device_num_rows, device_max_levels, device_out_ptrs, device_out_capacities, device_validity_ptrs,
+                               device_statuses, num_items, value_bytes, layout);
+}
+void CascadedManager::place_parquet_booleans(const uint8_t* const* device_value_ptrs, const size_t* device_value_bytes,
+                                             const size_t* device_value_starts, const size_t* device_num_values,
+                                             const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                                             const uint32_t* device_max_levels, uint8_t* const* device_out_ptrs,
+                                             const size_t* device_out_capacities, uint8_t* const* device_validity_ptrs,
+                                             hipcompStatus_t* device_statuses, size_t num_items)
+{
+  impl->core.place_booleans_call(device_value_ptrs, device_value_bytes, device_value_starts, device_num_values, device_level_ptrs,
+                                 device_num_rows, device_max_levels, device_out_ptrs, device_out_capacities, device_validity_ptrs,
+                                 device_statuses, num_items);
+}
+void CascadedManager::place_parquet_strings(const uint8_t* const* device_body_ptrs, const size_t* device_body_bytes,
+                                            const size_t* device_value_starts, const int32_t* const* device_value_offsets,
+                                            const size_t* device_num_values, const uint8_t* const* device_level_ptrs,
+                                            const size_t* device_num_rows, const uint32_t* device_max_levels,
+                                            int32_t* const* device_out_offsets, const size_t* device_offset_capacities,
+                                            uint8_t* const* device_out_bytes, const size_t* device_byte_capacities,
+                                            size_t* device_out_byte_counts, uint8_t* const* device_validity_ptrs,
+                                            hipcompStatus_t* device_statuses, size_t num_items, ParquetStringLayout layout)
+{
+  impl->core.place_strings_call(device_body_ptrs, device_body_bytes, device_value_starts, device_value_offsets, device_num_values,
+                                device_level_ptrs, device_num_rows, device_max_levels, device_out_offsets, device_offset_capacities,
+                                device_out_bytes, device_byte_capacities, device_out_byte_counts, device_validity_ptrs,
+                                device_statuses, num_items, layout);
 }
 
 // reference hipcompManagerFactory.cpp:44-148 (synchronises the stream, as there)

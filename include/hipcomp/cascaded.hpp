@@ -34,6 +34,20 @@ enum class ParquetDeltaOutput
   Offsets /* the stream holds the lengths of a DELTA_LENGTH_BYTE_ARRAY page: n + 1 Arrow offsets, 0 first */
 };
 
+/* how the fixed-width values of an item of place_parquet_values lie in its source */
+enum class ParquetValueLayout
+{
+  Plain,          /* value k at k * value_bytes: a PLAIN page body, or a decoded array */
+  ByteStreamSplit /* byte b of value k at b * num_values + k: a BYTE_STREAM_SPLIT page body */
+};
+
+/* where the bytes of value k of an item of place_parquet_strings lie, off being its offsets */
+enum class ParquetStringLayout
+{
+  LengthPrefixed, /* at 4 * (k + 1) + off[k]: a PLAIN BYTE_ARRAY body, off from index_parquet_dictionary */
+  Packed          /* at off[k]: DELTA_LENGTH_BYTE_ARRAY, off from decode_parquet_delta(..., Offsets) */
+};
+
 struct CascadedManager : hipcompManagerBase
 {
   /* device_id must be the current device */
@@ -148,6 +162,64 @@ struct CascadedManager : hipcompManagerBase
                                          size_t* device_out_byte_counts, /* may be null: the bytes, 0 of a refused item */
                                          uint8_t* const* device_validity_ptrs, /* may be null */
                                          hipcompStatus_t* device_statuses, size_t num_items);
+  /* The three calls that put the dense values of a page that is not dictionary-encoded -- a PLAIN or BYTE_STREAM_SPLIT
+     page body, or the array a decode_parquet_delta or decode_parquet_hybrid call wrote -- into their rows with the nulls
+     placed: an Arrow-shaped array of values, of bits, or of offsets and bytes, and a validity bitmap.  The contract is
+     the dictionary calls' above wherever it applies: every array in device memory; each call one launch on the
+     manager's stream, no scratch, no synchronisation; at most 2^20 items; an item the rules refuse is
+     hipcompErrorCannotDecompress, every count it reports 0 and no byte of its outputs written; no item's result depends
+     on another's.  Each throws before anything is launched: more than 2^20 items, a null mandatory array, a parameter
+     outside its range, one or two of the levels' three arrays without the rest, an unknown enum value.  Dense (the
+     three arrays of the levels null): rows = num_values.  With levels (UCHAR): row r is valid where level[r] ==
+     max_level, the j-th valid row gets value j; a level above max_level and valid rows that are not num_values refuse
+     the item.  The validity bitmap is Arrow's and optional, at any byte address.  device_value_starts may be null (every
+     start 0): the item's source begins start[i] bytes behind its pointer, the byte count being that of the whole buffer
+     from the pointer; a start above it refuses the item (the consumed bytes of a V1 page's definition levels, or of a
+     decode_parquet_delta(..., Offsets) call, go here as they are).  An item's inputs and outputs must not overlap; this
+     is not checked.  The contract, rule by rule: INTEGRATION.md, "PLAIN Parquet values placed in rows in the Cascaded
+     manager". */
+  /* 1. Fixed-width values of value_bytes (1 to 64) each.  Plain: value k lies at src + k * value_bytes, at any byte
+     address.  ByteStreamSplit: byte b of value k lies at src + b * num_values + k.  rows values are written, value_bytes
+     zero bytes where the row is not valid; the output lies at the alignment of the largest power of two that divides
+     value_bytes, at most 8.  Refused: rows above the capacity, num_values * value_bytes above the bytes behind the
+     start, and what the levels refuse. */
+  void place_parquet_values(const uint8_t* const* device_value_ptrs, const size_t* device_value_bytes,
+                            const size_t* device_value_starts, /* may be null */
+                            const size_t* device_num_values, const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                            const uint32_t* device_max_levels, /* these three: all null (dense) or all set */
+                            void* const* device_out_ptrs, const size_t* device_out_capacities, /* in values (rows) */
+                            uint8_t* const* device_validity_ptrs, /* may be null; (rows + 7) / 8 bytes per item */
+                            hipcompStatus_t* device_statuses, size_t num_items, uint32_t value_bytes, ParquetValueLayout layout);
+  /* 2. PLAIN BOOLEAN: value k is bit k & 7 of byte k >> 3.  The output is an Arrow boolean array's values bitmap,
+     (rows + 7) / 8 bytes at any byte address: bit r is the j-th source bit where row r is the j-th valid row, 0 where the
+     row is not valid, the unused bits 0.  Refused: (num_values + 7) / 8 above the bytes behind the start, rows above
+     the capacity, and what the levels refuse.  Bits behind num_values are not looked at. */
+  void place_parquet_booleans(const uint8_t* const* device_value_ptrs, const size_t* device_value_bytes,
+                              const size_t* device_value_starts, /* may be null */
+                              const size_t* device_num_values, const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                              const uint32_t* device_max_levels, /* these three: all null (dense) or all set */
+                              uint8_t* const* device_out_ptrs, const size_t* device_out_capacities, /* in rows (bits) */
+                              uint8_t* const* device_validity_ptrs, /* may be null */
+                              hipcompStatus_t* device_statuses, size_t num_items);
+  /* 3. BYTE_ARRAY values to an Arrow string array: rows + 1 offsets, 0 first, a row that is not valid adding 0, and the
+     valid rows' bytes back to back.  device_value_offsets are num_values + 1 INT offsets, not trusted.  LengthPrefixed:
+     a PLAIN body (len32 bytes len32 bytes ...) with the offsets index_parquet_dictionary writes for it; value k's
+     bytes lie at body + 4 * (k + 1) + off[k].  Packed: DELTA_LENGTH_BYTE_ARRAY with the offsets of
+     decode_parquet_delta(..., Offsets); value k's bytes lie at body + off[k].  Every value needs 0 <= off[k] <=
+     off[k + 1] and its end -- 4 * (k + 1) + off[k + 1], or off[k + 1] -- at most the bytes behind the start.  Refused
+     besides: rows + 1 above the offset capacity, a byte total above the byte capacity or above 2^31 - 1, and what the
+     levels refuse.  num_values may be the counts an earlier call leaves: a refused earlier item has 0 and refuses
+     every item with a valid row. */
+  void place_parquet_strings(const uint8_t* const* device_body_ptrs, const size_t* device_body_bytes,
+                             const size_t* device_value_starts, /* may be null */
+                             const int32_t* const* device_value_offsets, const size_t* device_num_values,
+                             const uint8_t* const* device_level_ptrs, const size_t* device_num_rows,
+                             const uint32_t* device_max_levels, /* these three: all null (dense) or all set */
+                             int32_t* const* device_out_offsets, const size_t* device_offset_capacities, /* elements */
+                             uint8_t* const* device_out_bytes, const size_t* device_byte_capacities,
+                             size_t* device_out_byte_counts, /* may be null: the bytes, 0 of a refused item */
+                             uint8_t* const* device_validity_ptrs, /* may be null */
+                             hipcompStatus_t* device_statuses, size_t num_items, ParquetStringLayout layout);
 
 private:
   struct Impl;
